@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
 """Headline benchmark: Pix2Pix `train_step` images/sec at 256x256 (BASELINE.json), bf16, batch 16 per GPU.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...; started WITHOUT a
    launcher, `--gpus N` spawns that command itself, one rank per GPU, before the parent touches a GPU)
 
 A "step" is one full Pix2Pix.train_step(training=True): generator forward, discriminator forward on
 real++fake, BCE/L1 losses, both backward passes (dgrad + wgrad), TF-form Adam on every weight, and (N>1)
 the RCCL gradient all-reduce - the whole step replayed from a captured hipGraph, inputs resident in HBM.
-Prints ONE JSON line (rank 0) with the step throughput, the roofline of the dominant GEMM kernel measured
-live with HIP events, and the CPU oracle timed on this box's host cores.
+Prints ONE JSON line (rank 0) with the step throughput.  A plain run sets up, warms up, times exactly K steps
+once and prints.  --full adds the secondary figures: the timed region repeated (median of 5), the sustained
+figure, the roofline of the dominant GEMM kernel measured live with HIP events, and the CPU oracle timed on
+the host's cores.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -107,6 +109,36 @@ def read_sclk_mhz(index=0):
     return best
 
 
+DUMP_MAX_ELEMS = 1 << 21        # per array: 8 MB of float32; larger arrays are written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, step, model):
+    """What the last step handed its caller, as float32 / float64 .npy files: the losses train_step returns, the generator output(s)
+    and every network's fp32 master weights after Adam.  An array over DUMP_MAX_ELEMS is written as the elements at a fixed set of
+    flat indices (numpy default_rng(0), sorted; the indices depend only on the array's size) under <name>.sample<size>."""
+    if model == 'pix2pix':
+        arrays = {'losses': step.losses[:4], 'gen_output': step.g.output_f32()}
+        nets = {'G': step.G, 'D': step.D}
+    else:
+        arrays = {'losses': step.losses[:7], 'fake_y': step.fy.output_f32(), 'fake_x': step.fx.output_f32()}
+        nets = {'Gg': step.Gg, 'Gf': step.Gf, 'Dx': step.Dx, 'Dy': step.Dy}
+    arrays.update({f'{k}.master': net.params.master for k, net in nets.items()})
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if name == 'losses':
+            a = a.astype(np.float64)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            name, a = f'{name}.sample{a.size}', a.reshape(-1)[idx]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB")
+        np.save(os.path.join(out_dir, f'{name}.npy'), a)
+
+
 CPU_BASELINE_THREADS = 16       # eager PyTorch-CPU train_step on the 128-core host: 1.53 / 2.42 / 1.69 / 1.07 / 0.36 img/s at 8 / 16 / 32 / 64 /
                                 # 128 threads (tools/cpu_threads_sweep.py): every core oversubscribes the BLAS / ATen pools
 
@@ -183,14 +215,20 @@ def main():
     ap.add_argument('--img-size', type=int, default=256)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f16', 'f32'])
     ap.add_argument('--model', default='pix2pix', choices=['pix2pix', 'cyclegan'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also the secondary measurements: repeats and sustain default to 5 and 3 s, the '
+                    'roofline / per-kernel classes (eager instrumented passes) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last one computed (losses, generator '
+                    'output, a fixed sample of the updated weights) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--no-graph', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true', help='skip the eager instrumented passes (profiler runs: only the replayed step in the trace)')
-    ap.add_argument('--gemm-only', action='store_true', help='also time the GEMM classes with plain epilogues (conv.bwd_fuse_tile = 3, a second step '
-                    'object: not the shipped plan) -> "kernels_gemm_only"')
+    ap.add_argument('--no-roofline', action='store_true', help='--full: skip the eager instrumented passes (profiler runs: only the replayed step in the trace)')
+    ap.add_argument('--gemm-only', action='store_true', help='--full: also time the GEMM classes with plain epilogues (conv.bwd_fuse_tile = 3, a second '
+                    'step object: not the shipped plan) -> "kernels_gemm_only"')
     ap.add_argument('--fp32-allreduce', action='store_true', help='exchange gradients as fp32 instead of bf16')
-    ap.add_argument('--repeats', type=int, default=5, help='the K-step timed region is run this many times; the median is reported')
-    ap.add_argument('--sustain', type=float, default=3.0, help='seconds of back-to-back steps for the "sustained" key (0: skip)')
+    ap.add_argument('--repeats', type=int, default=None, help='the K-step timed region is run this many times; the median is reported '
+                    '(default 1, with --full 5)')
+    ap.add_argument('--sustain', type=float, default=None, help='seconds of back-to-back steps for the "sustained" key (0: skip; default 0, '
+                    'with --full 3)')
     ap.add_argument('--single-stream', action='store_true', help='no side lanes: every launch of the captured step on one stream (profiling)')
     ap.add_argument('--exchange', default='allreduce', choices=['allreduce', 'rs_ag'],
                     help='gradient exchange: all-reduce per bucket, or fp32 reduce-scatter + all-gather in the wire format')
@@ -199,6 +237,12 @@ def main():
     ap.add_argument('--opt', action='append', default=[], metavar='KEY=VALUE',
                     help='planner option of the kernel library (gan_set_option, include/gan_amd.h); for A/B runs')
     args = ap.parse_args()
+    if args.gemm_only and not args.full:
+        ap.error('--gemm-only needs --full')
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.sustain is None:
+        args.sustain = 3.0 if args.full else 0.0
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # no launcher: start one rank per GPU ourselves (before this process initialises a GPU) and relay the result
@@ -303,6 +347,8 @@ def main():
             dt = float(t.item())
         times.append(dt)
     dt = sorted(times)[len(times) // 2]             # median over the repeats (max over ranks inside each)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step, args.model)
     # sustained figure: >= --sustain seconds of back-to-back steps (the timed region above is a few 0.2 s bursts)
     sustained = None
     if args.sustain > 0:
@@ -351,52 +397,52 @@ def main():
         # roofline of the dominant kernel class, measured live (eager, HIP events on the launch stream) ON THE SHIPPED PLAN: the
         # same step object, networks and planner options the timed region replayed (conv.bwd_fuse_tile = 1: some dgrad launches of
         # the class also start the layer-below backward in their epilogue - that time is inside the figure).
-        if args.no_roofline and world == 1 and not rehearse:
+        if not args.full or (args.no_roofline and world == 1 and not rehearse):
             print(json.dumps(out), flush=True)
-            return
-        prof = gemm_profile(step, inputs)
-        tot_ms = sum(v[0] for v in prof.values())
-        kname, (kms, kfl, kn) = max(prof.items(), key=lambda kv: kv[1][0])
-        ach = kfl / (kms * 1e-3) / 1e12
-        # HBM bytes per launch come from a separate rocprofv3 --pmc pass of this same command (counters cannot be
-        # collected inside this process); the committed summary is quoted and named, never re-measured here
-        traffic, traffic_src = None, None
-        for name in ('r05_pmc_traffic.json', 'r04_pmc_traffic.json', 'r03_pmc_traffic.json', 'r02_pmc_traffic.json', 'r01_pmc_traffic.json'):
-            try:
-                pmc = json.load(open(os.path.join(ROOT, 'profiles', name)))
-                if B == 16 and S == 256 and args.model == 'pix2pix' and kname in pmc:
-                    traffic, traffic_src = pmc[kname]["hbm_bytes_per_launch"], f"profiles/{name} (separate rocprofv3 --pmc pass, not this run)"
-                    break
-            except Exception:
-                pass
-        out["roofline"] = {"bound": "mfma", "kernel": kname, "achieved": round(ach, 1), "peak": MFMA_PEAK_TFLOPS,
-                           "unit": "TFLOP/s", "frac": round(ach / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                           "flops_per_launch": round(kfl / kn),
-                           "launches_per_step": kn, "avg_launch_us": round(kms / kn * 1e3, 2),
-                           "gemm_share_of_eager_gemm_time": round(kms / tot_ms, 3), "plan": "as shipped (the replayed step's own launches)",
-                           "event_bracket_us_subtracted": round(gemm_profile.bracket_ms * 1e3, 2),
-                           "timing": "HIP events around each launch of the class on its stream, eager single-stream passes of the SHIPPED "
-                                     "plan after the timed region; profiles/r05_bench_p16_kernel_stats_single_stream.csv carries the same "
-                                     "classes (columns class, flops_per_launch) from rocprofv3 --kernel-trace of the replayed graph"}
-        out["kernels"] = {k: {"ms_per_step": round(v[0], 4), "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1), "launches": v[2]}
-                          for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}
-        # secondary: the same GEMMs with plain epilogues (conv.bwd_fuse_tile = 3), on a second step object - NOT the shipped plan
-        if args.gemm_only and args.model == 'pix2pix' and not step.sync:
-            shipped_opt = _L.set_option('conv.bwd_fuse_tile', 3)
-            try:
-                pstep = Pix2PixStep(ctx, B, S, 1, lam=100.0, seed=123, nets=(step.G, step.D))
-                prof2 = gemm_profile(pstep, inputs)
-            finally:
-                _L.set_option('conv.bwd_fuse_tile', shipped_opt)
-            del pstep
-            out["kernels_gemm_only"] = {k: {"ms_per_step": round(v[0], 4), "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1), "launches": v[2]}
-                                        for k, v in sorted(prof2.items(), key=lambda kv: -kv[1][0])}
-        out["notes"] = ("inputs are pre-staged in the captured step's own input buffers (resident in HBM, no per-step staging copy); "
-                        "roofline / kernels are the shipped plan")
-        out["losses"] = [round(float(x), 5) for x in losses[:4]]
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline()
-        print(json.dumps(out), flush=True)
+        else:
+            prof = gemm_profile(step, inputs)
+            tot_ms = sum(v[0] for v in prof.values())
+            kname, (kms, kfl, kn) = max(prof.items(), key=lambda kv: kv[1][0])
+            ach = kfl / (kms * 1e-3) / 1e12
+            # HBM bytes per launch come from a separate rocprofv3 --pmc pass of this same command (counters cannot be
+            # collected inside this process); the committed summary is quoted and named, never re-measured here
+            traffic, traffic_src = None, None
+            for name in ('r05_pmc_traffic.json', 'r04_pmc_traffic.json', 'r03_pmc_traffic.json', 'r02_pmc_traffic.json', 'r01_pmc_traffic.json'):
+                try:
+                    pmc = json.load(open(os.path.join(ROOT, 'profiles', name)))
+                    if B == 16 and S == 256 and args.model == 'pix2pix' and kname in pmc:
+                        traffic, traffic_src = pmc[kname]["hbm_bytes_per_launch"], f"profiles/{name} (separate rocprofv3 --pmc pass, not this run)"
+                        break
+                except Exception:
+                    pass
+            out["roofline"] = {"bound": "mfma", "kernel": kname, "achieved": round(ach, 1), "peak": MFMA_PEAK_TFLOPS,
+                               "unit": "TFLOP/s", "frac": round(ach / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                               "flops_per_launch": round(kfl / kn),
+                               "launches_per_step": kn, "avg_launch_us": round(kms / kn * 1e3, 2),
+                               "gemm_share_of_eager_gemm_time": round(kms / tot_ms, 3), "plan": "as shipped (the replayed step's own launches)",
+                               "event_bracket_us_subtracted": round(gemm_profile.bracket_ms * 1e3, 2),
+                               "timing": "HIP events around each launch of the class on its stream, eager single-stream passes of the SHIPPED "
+                                         "plan after the timed region; profiles/r05_bench_p16_kernel_stats_single_stream.csv carries the same "
+                                         "classes (columns class, flops_per_launch) from rocprofv3 --kernel-trace of the replayed graph"}
+            out["kernels"] = {k: {"ms_per_step": round(v[0], 4), "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1), "launches": v[2]}
+                              for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}
+            # secondary: the same GEMMs with plain epilogues (conv.bwd_fuse_tile = 3), on a second step object - NOT the shipped plan
+            if args.gemm_only and args.model == 'pix2pix' and not step.sync:
+                shipped_opt = _L.set_option('conv.bwd_fuse_tile', 3)
+                try:
+                    pstep = Pix2PixStep(ctx, B, S, 1, lam=100.0, seed=123, nets=(step.G, step.D))
+                    prof2 = gemm_profile(pstep, inputs)
+                finally:
+                    _L.set_option('conv.bwd_fuse_tile', shipped_opt)
+                del pstep
+                out["kernels_gemm_only"] = {k: {"ms_per_step": round(v[0], 4), "tflops": round(v[1] / (v[0] * 1e-3) / 1e12, 1), "launches": v[2]}
+                                            for k, v in sorted(prof2.items(), key=lambda kv: -kv[1][0])}
+            out["notes"] = ("inputs are pre-staged in the captured step's own input buffers (resident in HBM, no per-step staging copy); "
+                            "roofline / kernels are the shipped plan")
+            out["losses"] = [round(float(x), 5) for x in losses[:4]]
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline()
+            print(json.dumps(out), flush=True)
     if world > 1 or rehearse:
         dist.barrier()                     # rank 0 has been profiling alone: every rank leaves the group together
         dist.destroy_process_group()

@@ -866,3 +866,34 @@ def test_layer_stacks_in_the_captured_steps_change_nothing(model, planner_option
     assert np.array_equal(np.array(l0), np.array(l1)), (l0, l1)
     for a, b in zip(w0_ + s0, w1_ + s1):
         assert torch.equal(a, b)
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_identical_outputs(tmp_path):
+    """bench.py without --full times exactly --steps steps once and prints the headline keys without the --full figures;
+    --dump-outputs writes the last step's losses, generator output and weight samples as float64 / float32 .npy, and two runs
+    with the same arguments write the same values (seeded synthetic inputs, deterministic captured step)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / f'dump{k}')
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '2', '--dump-outputs', d],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+        assert out['steps'] == 3 and out['repeats'] == 1 and len(out['ms_per_step_all_repeats']) == 1 and out['sustained'] is None
+        assert out['unit'] == 'images/sec' and out['higher_is_better'] is True and out['dtype'] == 'bf16' and out['ms_per_step'] > 0
+        assert abs(out['value'] - 16e3 / out['ms_per_step']) < 1e-2 * out['value']
+        assert not {'roofline', 'kernels', 'cpu_baseline'} & set(out), sorted(out)
+        arrs = {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert arrs['losses.npy'].shape == (4,) and arrs['gen_output.npy'].shape == (16, 256, 256, 1)
+        assert sum(f.startswith('G.master') for f in arrs) == 1 and sum(f.startswith('D.master') for f in arrs) == 1 and len(arrs) == 4
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f

@@ -3,7 +3,7 @@
 tag=${1:-r02}
 out=gpurun_out/configs_$tag.jsonl
 : > $out
-run() { python3 bench.py --steps 20 --warmup 5 --repeats 3 --no-cpu-baseline "$@" 2>/dev/null >> $out; }
+run() { python3 bench.py --full --steps 20 --warmup 5 --repeats 3 --no-cpu-baseline "$@" 2>/dev/null >> $out; }
 run                                                  # config 2: Pix2Pix 256 bf16 batch 16
 run --batch 64
 run --dtype f16

@@ -3,11 +3,12 @@
 # summaries are copied into profiles/ afterwards): kernel-trace statistics and separate PMC passes (FETCH_SIZE, WRITE_SIZE,
 # SQ_*), exactly the command the driver runs with fewer steps.
 tag=${1:-r05}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out/profiles_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 CMD="python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --repeats 1 --no-cpu-baseline --sustain 0 --no-roofline"
-python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > $out/bench_p16.json 2> $out/bench.err
+python3 "$ROOT/bench.py" --full --no-cpu-baseline > $out/bench_p16.json 2> $out/bench.err
 # kernel statistics on the driver's own command line (20 timed steps); --no-roofline: the trace holds the 25 replays of the captured
 # step (20 timed + 5 warm-up) + ONE eager warm-up step of capture(), no instrumented eager passes: per-step figures = totals / 26
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --repeats 1 --no-cpu-baseline --sustain 0 --no-roofline > $out/bench_under_rocprof.json 2>> $out/bench.err
