@@ -1,0 +1,815 @@
+"""Launch audit of a captured training step (helper of tests/test_gpu_launch_audit.py; not a conftest).
+
+record(): every library call the step's capture body makes (Ctx.capture_graph's fn: the eager warm-up step is left out), with the
+descriptors the step itself built.  replay(): the recorded calls re-issued one at a time, in recorded order, on one stream; before
+each call the regions it reads and writes are snapshot through the HIP runtime torch loaded (gan_amd/_lib.py: one runtime per
+process), after it the outputs are read back and compared with an fp64 reference computed from the snapshot - so no error
+compounds across layers and every gate is a rounding bound of that one call (GATES below).
+
+Every recorded entry point either has a checker here or is named in ALLOWLIST with the reason it is not checked; a call that has
+neither fails the audit."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import re
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from gan_amd import _lib as L
+
+# ---- gates ------------------------------------------------------------------------------------------------------------------
+# A stored 16-bit value: |got - ref| <= K_ULP * ulp(ref) + C_ACC * EPS32 * sum|terms|.  K_ULP = 1: round-to-nearest storage is half an
+# ulp off the exact fp32 result, and the other half covers a ref that sits on the other side of a binade edge.  C_ACC: the fp32
+# accumulation of at most ~2^12 partial sums per output (16 taps x K/32 MFMA blocks x split-K slabs): the random-walk error of such a
+# blocked sum stays within sqrt(4096) = 64 unit roundoffs of sum|terms| (the worst-case bound, 4096 eps, would hide a lost slab).
+# sum|terms| is the cheap upper bound max|x| * sum|w| per output channel (abs_bound; for wgrad max|big| * sum|small| per column):
+# an exact |x| x |w| pass would double the reference's cost, and the term only matters where the result cancels.
+# fp32 outputs (exact-MFMA path, slabs, partials): the same formula, ulp of fp32.  The finishing slab reduce (GanNormFuse) and the
+# fused backward epilogue round the conv result to storage before they use it (splitk_norm.h: "as stored"): the forward form is
+# checked against the stored y it wrote, the backward form (whose da is never stored) carries one extra ulp of da, times the
+# derivative, through dz, the statistics and dy.
+EPS32 = 2.0 ** -23
+C_ACC = 64.0
+K_ULP = 1.0
+MANT = {L.F32: 23, L.BF16: 7, L.F16: 10}
+MIN_ULP = {L.F32: 2.0 ** -149, L.BF16: 2.0 ** -133, L.F16: 2.0 ** -24}
+TDT = {L.F32: torch.float32, L.BF16: torch.bfloat16, L.F16: torch.float16}
+ACC = C_ACC * EPS32
+
+# Entry points the planner / builder only QUERY (host side, enqueue nothing): passed straight through, never recorded.
+QUERIES = {'gan_conv_plan_info', 'gan_conv_workspace_bytes', 'gan_wgrad_plan_info', 'gan_wgrad_workspace_bytes', 'gan_conv_tap_shared',
+           'gan_wgrad_adam_fused', 'gan_wgrad_wire_direct', 'gan_conv_stack_eligible', 'gan_conv_stack_plan_bytes', 'gan_conv_stack_plan',
+           'gan_conv_stack_barrier_bytes', 'gan_norm_workspace_bytes', 'gan_norm_sync_bytes', 'gan_norm_sync_error_offset',
+           'gan_set_option', 'gan_get_option', 'gan_launch_log', 'gan_version', 'gan_crc32c'}
+
+# Recorded entry points that are not checked here, and why.
+ALLOWLIST = {
+    'gan_bce_logits': 'loss scalar + (sigmoid(x)-t)/n row: elementwise, checked against the oracle by test_gpu_ops::test_act_bwd_bias_grad_losses',
+    'gan_patchgan_losses': 'the three BCE terms in one pass: test_gpu_ops::test_patchgan_losses_equal_three_bce_calls + the step tests',
+    'gan_l1': 'mean |a-b| scalar + sign row: test_gpu_ops::test_act_bwd_bias_grad_losses',
+    'gan_sum3': 'three scalars added: the step tests compare the total generator loss with the oracle',
+    'gan_adam_begin': 'step counter + lr_t scalar: read back here as the input of every fused-Adam check (a wrong lr_t fails those)',
+    'gan_adam_tf': 'Adam of the norm / bias vectors (no planner choice): test_gpu_ops::test_adam_tf_and_weight_prep',
+    'gan_adam_prepare_multi': 'the flat multi-tensor Adam + NK refresh: test_gpu_ops::test_fused_adam_prepare_equals_adam_then_prepare; '
+                              'the NK copies it writes are the weights every later conv reads, decoded from the device here',
+    'gan_weights_prepare_multi': 'NK copies of the master: decoded from the device copy by every conv check here (not trusted)',
+    'gan_pack': 'fp32 -> storage cast of the inputs: test_gpu_ops::test_dropout_mask_and_pack',
+    'gan_pack_multi': 'test_gpu_ops::test_multi_launch_pack_and_dropout_equal_single_calls',
+    'gan_unpack': 'test_gpu_ops::test_dropout_mask_and_pack',
+    'gan_copy_view': 'a typed copy between views: its destination is an input read from the snapshot by the next checked call',
+    'gan_dropout_mask': 'counter-hash Bernoulli mask (no reference value exists): read here as an input of every dropout check',
+    'gan_dropout_mask_multi': 'as gan_dropout_mask: test_gpu_ops::test_multi_launch_pack_and_dropout_equal_single_calls',
+    'gan_grads_check': 'fp16 inf/nan flag of the loss scale: test_gpu_configs::test_loss_scale_state_machine, '
+                       'test_gpu_configs::test_pix2pix_f16_step_vs_oracle',
+    'gan_loss_scale_update': 'fp16 loss-scale state machine: test_gpu_configs::test_loss_scale_state_machine',
+    'gan_grad_pack': 'data-parallel wire format (out of scope: multi-rank paths)',
+    'gan_grad_unpack': 'data-parallel wire format (out of scope: multi-rank paths)',
+    'gan_conv_stack_launch': 'layer stacks (conv.stack, off by default; out of scope)',
+    'gan_norm_stats_partial': 'norm.fin_in_apply only (off by default; out of scope)',
+    'gan_norm_finalize_act_fwd': 'norm.fin_in_apply only (off by default; out of scope)',
+}
+
+
+def ulp(ref, dt):
+    """ulp of the storage type at |ref| (fp64 tensor)."""
+    _, e = torch.frexp(ref.abs())
+    u = torch.ldexp(torch.ones_like(ref), (e - 1 - MANT[dt]).to(torch.int32))
+    return torch.where(ref == 0, MIN_ULP[dt], torch.clamp(u, min=MIN_ULP[dt]))
+
+
+def ratio(got, ref, gate):
+    """Worst |got - ref| / gate (0 for empty)."""
+    if got.numel() == 0:
+        return 0.0
+    d = (got.double() - ref.double()).abs()
+    if not torch.isfinite(got.double()).all():
+        return math.inf
+    return float((d / gate.clamp(min=1e-300)).max())
+
+
+# ---- device memory through torch's HIP runtime ---------------------------------------------------------------------------------
+_hip = None
+
+
+def hip():
+    global _hip
+    if _hip is None:
+        path = None
+        with open('/proc/self/maps') as f:           # the libamdhip64 torch loaded (gan_amd/_lib.py: ONE runtime per process)
+            for ln in f:
+                if 'libamdhip64' in ln:
+                    path = ln.split()[-1]
+                    break
+        if path is None:
+            raise RuntimeError("the HIP runtime is not loaded (import torch and touch the GPU first)")
+        _hip = C.CDLL(path)
+        _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        _hip.hipMemcpy.restype = C.c_int
+    return _hip
+
+
+def read(ptr, count, dt=L.F32, tdtype=None):
+    """count elements at device address ptr -> CPU tensor (storage type)."""
+    t = torch.empty(int(count), dtype=tdtype or TDT[dt])
+    if count:
+        rc = hip().hipMemcpy(t.data_ptr(), ptr, t.numel() * t.element_size(), 2)      # hipMemcpyDeviceToHost
+        if rc:
+            raise RuntimeError(f"hipMemcpy D2H failed ({rc})")
+    return t
+
+
+class View:
+    """Snapshot of a GanTensor: the whole span it addresses (pixels x pitch, last pixel up to c) and its dense [n,h,w,c] part."""
+
+    def __init__(self, t, dt):
+        self.t, self.dt = t, dt
+        self.rows = t.n * t.h * t.w
+        self.span = (self.rows - 1) * t.pitch + t.c if self.rows else 0
+        self.raw = read(t.ptr, self.span, dt)
+
+    def dense(self):
+        t = self.t
+        return torch.as_strided(self.raw, (t.n, t.h, t.w, t.c), (t.h * t.w * t.pitch, t.w * t.pitch, t.pitch, 1)).double()
+
+    def changed_channels(self, other):
+        """channel index (position % pitch) of every stored element that differs bitwise from `other`'s snapshot of the span."""
+        it = torch.int16 if self.raw.element_size() == 2 else torch.int32
+        pos = (self.raw.view(it) != other.raw.view(it)).nonzero().reshape(-1)
+        return pos % self.t.pitch
+
+
+def untouched(before, after, c0, c1):
+    """Gate entry for stored bytes a call must not change: everything in the span outside channels [c0, c1)."""
+    ch = before.changed_channels(after)
+    return math.inf if int(((ch < c0) | (ch >= c1)).sum()) else 0.0
+
+
+def unchanged(before, after, c0, c1):
+    """Gate entry: channels [c0, c1) of the span must keep their bits."""
+    ch = before.changed_channels(after)
+    return math.inf if int(((ch >= c0) & (ch < c1)).sum()) else 0.0
+
+
+# ---- fp64 references --------------------------------------------------------------------------------------------------------
+def nchw(x):
+    return x.permute(0, 3, 1, 2).contiguous()
+
+
+def nhwc(x):
+    return x.permute(0, 2, 3, 1).contiguous()
+
+
+def conv_ref(op, x, w, stride):
+    """The four conv entry points from the device operand w[16][rows][x.c] (row = y channel, column = x channel for all four).
+    op 0 conv_fwd / 3 convT_dgrad gather from the fine grid, op 1 conv_dgrad / 2 convT_fwd scatter onto it:
+    y[o] = sum_tap w[tap] x[o*s - 1 + tap]  /  y[o*s - 1 + tap] += w[tap] x[o]   (tap = kh*4 + kw)."""
+    yc, xc = w.shape[1], w.shape[2]
+    w4 = w.reshape(4, 4, yc, xc)
+    if op in (0, 3):
+        return nhwc(F.conv2d(nchw(x), w4.permute(2, 3, 0, 1).contiguous(), stride=stride, padding=1))
+    return nhwc(F.conv_transpose2d(nchw(x), w4.permute(3, 2, 0, 1).contiguous(), stride=stride, padding=1))
+
+
+def abs_bound(x, w):
+    """Upper bound of sum|terms| of every output of conv_ref: max|x| times the sum of |w| over taps and x channels of its y channel
+    (per channel, broadcast over pixels - the cheap bound; the exact one, conv_ref(|x|, |w|), doubles the reference's cost)."""
+    return float(x.abs().max()) * w.abs().sum((0, 2))
+
+
+def wgrad_ref(big, small, stride, big_c, small_c):
+    """dw[tap][b][s] = sum_{n,o} big[n, o*s - 1 + tap, b] small[n, o, s] (HWIO for Conv2D, (kh,kw,cout,cin) for Conv2DTranspose)."""
+    bg, sm = nchw(big[..., :big_c]), nchw(small[..., :small_c])
+    dw = torch.nn.grad.conv2d_weight(bg, (small_c, big_c, 4, 4), sm, stride=stride, padding=1)
+    return dw.permute(2, 3, 1, 0).reshape(16, big_c, small_c)
+
+
+def act_f(z, act, slope):
+    if act == L.ACT_LRELU:
+        return torch.where(z > 0, z, z * slope)
+    if act == L.ACT_RELU:
+        return z.clamp(min=0)
+    if act == L.ACT_TANH:
+        return torch.tanh(z)
+    return z
+
+
+def act_d(z, act, slope):
+    """(derivative, derivative on the other side of the kink): z is the pre-activation value (for tanh: the activation)."""
+    if act == L.ACT_LRELU:
+        return torch.where(z > 0, 1.0, slope).double(), torch.where(z >= 0, 1.0, slope).double()
+    if act == L.ACT_RELU:
+        return (z > 0).double(), (z >= 0).double()
+    if act == L.ACT_TANH:
+        d = 1.0 - z * z
+        return d, d
+    one = torch.ones_like(z)
+    return one, one
+
+
+def kink_d(z, zbound, act, slope):
+    """Derivative where the fp32 z of the kernel may sit on either side of a kink (|z| <= its rounding bound): both accepted."""
+    d, d2 = act_d(z, act, slope)
+    near = z.abs() <= zbound
+    lo = torch.where(near, torch.minimum(d, d2), d)
+    hi = torch.where(near, torch.maximum(d, d2), d)
+    return lo, hi
+
+
+def between(got, lo, hi, gate):
+    """|got - [lo, hi]| / gate: an interval reference (an element whose derivative may be taken on either side of a kink)."""
+    g = got.double()
+    if not torch.isfinite(g).all():
+        return math.inf
+    d = torch.clamp(lo - g, min=0) + torch.clamp(g - hi, min=0)
+    return float((d / gate.clamp(min=1e-300)).max()) if d.numel() else 0.0
+
+
+def grp(t, groups):
+    """[n,h,w,c] -> [groups, rows per group, c]"""
+    return t.reshape(groups, -1, t.shape[-1])
+
+
+def stats_gate(y, ey, groups):
+    """mean / biased variance of y ([n,h,w,c], fp64) per group and the bounds of the kernel's values: ey = per-element bound of the
+    y the kernel summed, plus the fp32 accumulation of the sums."""
+    yg, eg = grp(y, groups), grp(ey, groups)
+    R = yg.shape[1]
+    m = yg.mean(1)
+    var = torch.clamp(((yg - m.unsqueeze(1)) ** 2).mean(1), min=0.0)
+    dm = eg.mean(1) + ACC * yg.abs().mean(1)
+    dvar = ACC * (yg * yg).mean(1) + 2 * (yg.abs() * eg).mean(1) + 2 * m.abs() * dm
+    return m, var, dm, dvar, R
+
+
+def rstd_of(var, dvar, eps):
+    r = 1.0 / torch.sqrt(var + eps)
+    dr = 0.5 * r ** 3 * dvar + 4 * EPS32 * r
+    return r, dr
+
+
+# ---- recording ----------------------------------------------------------------------------------------------------------------
+class Call:
+    def __init__(self, name, fn, args):
+        self.name, self.fn, self.args = name, fn, args
+        self.label = ''
+        self.result = None
+
+
+class _Wrap:
+    def __init__(self, rec, name, fn):
+        self.rec, self.name, self.fn = rec, name, fn
+
+    def __call__(self, *args):
+        if self.rec.active:
+            self.rec.calls.append(Call(self.name, self.fn, args))
+        return self.fn(*args)
+
+
+class Recorder:
+    """Wraps the gan_* entry points of the loaded library (before the step object is built: the op lists hold the bound functions)
+    and records the calls made while Ctx.capture_graph runs its body."""
+
+    def __init__(self, monkeypatch):
+        self.lib = L.load()
+        self.calls, self.active = [], False
+        self.orig = {}
+        for name in L.SYMBOLS:
+            if name in QUERIES:
+                continue
+            fn = getattr(self.lib, name)
+            self.orig[name] = fn
+            monkeypatch.setattr(self.lib, name, _Wrap(self, name, fn))
+
+    def hook_capture(self, monkeypatch):
+        """Record inside the body of every Ctx.capture_graph (patched on the class: an instance attribute would tie the context into a
+        reference cycle whose later collection - inside another capture - destroys graphs mid-capture)."""
+        from gan_amd.nets import Ctx
+        orig = Ctx.capture_graph
+        rec = self
+
+        def capture_graph(ctx, fn, *a, **k):
+            def body():
+                rec.active = True
+                try:
+                    fn()
+                finally:
+                    rec.active = False
+            return orig(ctx, body, *a, **k)
+        monkeypatch.setattr(Ctx, 'capture_graph', capture_graph)
+
+
+def label_calls(calls, step):
+    """Layer label of every call: the op tuple that holds its descriptor (label + shape), and the network tensor its weight /
+    gradient pointer lies in."""
+    by_addr = {}
+    seen = set()
+
+    def walk(o, depth=0):
+        if id(o) in seen or depth > 4:
+            return
+        seen.add(id(o))
+        if isinstance(o, (list, tuple)):
+            if len(o) >= 3 and callable(o[0]) and isinstance(o[1], tuple) and isinstance(o[2], str):
+                for a in o[1]:
+                    obj = getattr(a, '_obj', None)
+                    if obj is not None:
+                        meta = o[3] if len(o) > 3 and isinstance(o[3], dict) else {}
+                        by_addr[C.addressof(obj)] = f"{o[2]} {meta.get('shape', '')}".strip()
+                return
+            for e in o:
+                walk(e, depth + 1)
+        elif isinstance(o, dict):
+            for e in o.values():
+                walk(e, depth + 1)
+        elif hasattr(o, '__dict__') and type(o).__module__.startswith('gan_amd'):
+            for e in vars(o).values():
+                walk(e, depth + 1)
+    walk(step)
+    ranges = []
+    nets = step.nets() if hasattr(step, 'nets') else []
+    tags = ['G', 'D'] if len(nets) == 2 else ['Gg', 'Gf', 'Dx', 'Dy'][:len(nets)]
+    for tag, net in zip(tags, nets):
+        P = net.params
+        for name, (o, shape) in P.entries.items():
+            n = int(np.prod(shape))
+            for which in ('master', 'grad', 'm', 'v'):
+                base = getattr(P, which).data_ptr() + 4 * o
+                ranges.append((base, base + 4 * n, f"{tag}.{name}"))
+        for name in P.nat:
+            for t in (P.nat[name], P.tr[name]):
+                ranges.append((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), f"{tag}.{name}"))
+
+    def owner(ptr):
+        for a, b, nm in ranges:
+            if ptr and a <= ptr < b:
+                return nm
+        return ''
+    for c in calls:
+        obj = getattr(c.args[0], '_obj', None) if c.args else None
+        lab = by_addr.get(C.addressof(obj), '') if obj is not None else ''
+        w = ''
+        if isinstance(obj, L.GanConvDesc):
+            w = owner(obj.w)
+        elif isinstance(obj, L.GanWgradDesc):
+            w = owner(obj.dw) or (owner(L.GanAdamFuse.from_address(obj.adam_fuse).master) if obj.adam_fuse else '')
+        elif isinstance(obj, (L.GanNormDesc, L.GanNormBwdDesc)):
+            w = owner(obj.gamma)
+        c.label = (w + ' ' + lab).strip() or c.name
+
+
+# ---- checkers: generators that snapshot, yield (the call runs), then read back and return {item: worst error / gate} --------------
+OPS = {'gan_conv2d_fwd': 0, 'gan_conv2d_dgrad': 1, 'gan_convT2d_fwd': 2, 'gan_convT2d_dgrad': 3}
+
+
+def conv_plan(d, op):
+    info = (C.c_int32 * 5)()
+    L.check(L.load().gan_conv_plan_info(C.byref(d), op, info), "conv_plan_info")
+    ts = L.load().gan_conv_tap_shared(C.byref(d), op)
+    return list(info), ts
+
+
+def check_conv(call):
+    d = call.args[0]._obj
+    op = OPS[call.name]
+    dt = d.dtype
+    info, ts = conv_plan(d, op)
+    bf = L.GanBwdFuse.from_address(d.bwd_fuse) if d.bwd_fuse else None
+    nf = L.GanNormFuse.from_address(d.norm_fuse) if d.norm_fuse else None
+    full = info[4] == -1 and nf is not None
+    partials = info[4] > 0 and d.stats_partial and d.stats_groups > 0
+    call.plan = f"op{op} tile {info[0]}x{info[1]} split {info[2]} par {info[3]} stats {info[4]} ts {ts}" + \
+        (" bwd_fuse" if bf else "") + (" norm_fuse" if full else "")
+    ydt = L.F32 if d.y_f32 else dt
+    xv = View(d.x, dt)
+    x = xv.dense()
+    w = read(d.w, 16 * d.w_rows * d.x.c, dt).double().reshape(16, d.w_rows, d.x.c)[:, :d.y.c]
+    bias = read(d.bias, d.y.c).double() if d.bias else None
+    y0 = View(d.y, ydt)
+    pre = {}
+    if bf is not None:
+        pre['ref'] = View(bf.ref, dt).dense()
+        pre['add'] = View(bf.add, dt).dense() if bf.add.ptr else None
+        G = d.stats_groups if bf.mean else 0
+        if bf.mean:
+            pre['mean'] = read(bf.mean, G * bf.cols).double().reshape(G, bf.cols)
+            pre['rstd'] = read(bf.rstd, G * bf.cols).double().reshape(G, bf.cols)
+            pre['gamma'] = read(bf.gamma, bf.cols).double()
+            pre['beta'] = read(bf.beta, bf.cols).double()
+        if bf.dropmask:
+            pre['mask'] = _mask(bf.dropmask, d.y.n, d.y.h, d.y.w, bf.cols, bf.mask_pitch)
+    if full:
+        out0 = View(nf.out, dt)
+        G = d.stats_groups
+        C_ = nf.out.c
+        if nf.gamma:
+            pre['ngamma'] = read(nf.gamma, C_).double()
+            pre['nbeta'] = read(nf.beta, C_).double()
+        if nf.moving_mean:
+            pre['mm'] = read(nf.moving_mean, C_).double()
+            pre['mv'] = read(nf.moving_var, C_).double()
+        if nf.dropmask:
+            pre['nmask'] = _mask(nf.dropmask, d.y.n, d.y.h, d.y.w, C_, C_)
+        if nf.dgamma:
+            pre['dg'] = read(nf.dgamma, C_).double()
+            pre['db'] = read(nf.dbeta, C_).double()
+    yield
+    res = {}
+    y1 = View(d.y, ydt)
+    yg = y1.dense()
+    ref = conv_ref(op, x, w, d.stride)
+    S = abs_bound(x, w).expand_as(ref)
+    assert tuple(ref.shape) == (d.y.n, d.y.h, d.y.w, d.y.c), (call.name, tuple(ref.shape), (d.y.n, d.y.h, d.y.w, d.y.c))
+    if bias is not None:
+        ref = ref + bias
+        S = S + bias.abs()
+    eacc = ACC * S                                   # fp32 accumulation bound of each (pre-activation) output
+    if bf is None:
+        out = act_f(ref, d.act, d.slope)
+        res['y'] = ratio(yg, out, K_ULP * ulp(out, ydt) + eacc)
+        res['y untouched outside y.c'] = untouched(y0, y1, 0, d.y.c)
+        if partials:
+            G = d.stats_groups
+            chunks = info[4]
+            p = read(d.stats_partial, G * chunks * d.y.c * 2).double().reshape(G, chunks, d.y.c, 2).sum(1)
+            ys = grp(yg, G)                          # the epilogues sum the STORED values (conv_gemm.hip): no rounding allowance
+            res['stats sum'] = ratio(p[..., 0], ys.sum(1), ACC * ys.abs().sum(1))
+            res['stats sumsq'] = ratio(p[..., 1], (ys * ys).sum(1), ACC * (ys * ys).sum(1))
+        if full:
+            res.update(_norm_fuse_fwd(d, nf, pre, out0, ref, eacc, yg, dt))
+        return res
+    # dgrad with the layer-below backward in its epilogue (GanBwdFuse)
+    cols = bf.cols
+    da = ref[..., :cols]
+    ea = eacc[..., :cols] + K_ULP * ulp(da, dt)      # the epilogue rounds da to storage before it adds `add` ("as stored")
+    if pre['add'] is not None:
+        da = da + pre['add'][..., :cols]
+        ea = ea + ACC * pre['add'][..., :cols].abs()
+    m2 = 2.0 * pre['mask'] if 'mask' in pre else torch.ones_like(da)
+    G = d.stats_groups if bf.mean else 1
+    if bf.mean:
+        r = pre['ref'][..., :cols]
+        rg = grp(r, G)
+        xhat = ((rg - pre['mean'].unsqueeze(1)) * pre['rstd'].unsqueeze(1)).reshape(r.shape)
+        z = grp(xhat, G) * pre['gamma'] + pre['beta']
+        zb = 8 * EPS32 * (grp(xhat, G).abs() * pre['gamma'].abs() + pre['beta'].abs()) + 1e-30
+        lo, hi = kink_d(z.reshape(r.shape), zb.reshape(r.shape), bf.act, bf.slope)
+    else:
+        a = pre['ref'][..., :cols]
+        lo, hi = kink_d(a, torch.zeros_like(a), bf.act, bf.slope)     # act'(a): a == 0 takes either side
+    zlo, zhi = torch.minimum(da * lo * m2, da * hi * m2), torch.maximum(da * lo * m2, da * hi * m2)
+    ez = ea * hi.abs() * m2
+    if not full:
+        res['dz'] = between(yg[..., :cols], zlo, zhi, K_ULP * ulp(zhi, dt) + ez)
+        if d.y.c > cols:
+            rest = ref[..., cols:]
+            res['plain gradient c>=cols'] = ratio(yg[..., cols:], rest, K_ULP * ulp(rest, dt) + eacc[..., cols:])
+        res['y untouched outside y.c'] = untouched(y0, y1, 0, d.y.c)
+        if partials and bf.mean:
+            chunks = info[4]
+            p = read(d.stats_partial, G * chunks * cols * 2).double().reshape(G, chunks, cols, 2).sum(1)
+            dz = grp(yg[..., :cols], G)                  # the stored dz (checked above), its unrounded value within half an ulp
+            xh = grp(xhat, G)
+            u = 0.5 * ulp(dz, dt)
+            res['bwd sum dz'] = ratio(p[..., 0], dz.sum(1), ACC * dz.abs().sum(1) + u.sum(1))
+            res['bwd sum dz*xhat'] = ratio(p[..., 1], (dz * xh).sum(1), ACC * (dz * xh).abs().sum(1) + (u * xh.abs()).sum(1) +
+                                           4 * EPS32 * (dz * xh).abs().sum(1))
+        return res
+    # GanNormFuse backward: the launch finishes the layer below (dy, dgamma, dbeta); dz never stored
+    out1 = View(nf.out, dt)
+    res['y[:cols] untouched'] = unchanged(y0, y1, 0, cols)
+    res['y untouched outside y.c'] = untouched(y0, y1, 0, d.y.c)
+    if d.y.c > cols:
+        rest = ref[..., cols:]
+        res['plain gradient c>=cols'] = ratio(yg[..., cols:], rest, K_ULP * ulp(rest, dt) + eacc[..., cols:])
+    # the kink interval is narrow (|z| within a few eps): take the derivative of the reference side, count the rest as its bound
+    dz = da * lo * m2
+    edz = ez + (da * (hi - lo) * m2).abs()
+    xh = grp(xhat, G)
+    dzg, eg = grp(dz, G), grp(edz, G)
+    R = dzg.shape[1]
+    s1, s2 = dzg.mean(1, keepdim=True), (dzg * xh).mean(1, keepdim=True)
+    e1 = eg.mean(1, keepdim=True) + ACC * dzg.abs().mean(1, keepdim=True)
+    e2 = (eg * xh.abs()).mean(1, keepdim=True) + ACC * (dzg * xh).abs().mean(1, keepdim=True)
+    gr = (pre['gamma'] * pre['rstd']).unsqueeze(1)
+    dy = gr * (dzg - s1 - xh * s2)
+    edy = gr.abs() * (eg + e1 + xh.abs() * e2) + 4 * EPS32 * gr.abs() * (dzg.abs() + s1.abs() + (xh * s2).abs())
+    got = grp(out1.dense(), G)
+    res['norm_fuse dy'] = ratio(got, dy, K_ULP * ulp(dy, dt) + edy)
+    res['norm_fuse out untouched outside c'] = untouched(out0, out1, 0, nf.out.c)
+    if nf.dgamma:
+        acc = float(nf.accumulate)
+        dg = read(nf.dgamma, cols).double()
+        db = read(nf.dbeta, cols).double()
+        rg_ = (dzg * xh).sum((0, 1)) + acc * pre['dg']
+        rb_ = dzg.sum((0, 1)) + acc * pre['db']
+        res['norm_fuse dgamma'] = ratio(dg, rg_, (eg * xh.abs()).sum((0, 1)) + ACC * ((dzg * xh).abs().sum((0, 1)) + acc * pre['dg'].abs()))
+        res['norm_fuse dbeta'] = ratio(db, rb_, eg.sum((0, 1)) + ACC * (dzg.abs().sum((0, 1)) + acc * pre['db'].abs()))
+    return res
+
+
+def _mask(ptr, n, h, w, c, pitch):
+    raw = read(ptr, (n * h * w - 1) * pitch + c, tdtype=torch.uint8)
+    return torch.as_strided(raw, (n, h, w, c), (h * w * pitch, w * pitch, pitch, 1)).double()
+
+
+def _norm_fuse_fwd(d, nf, pre, out0, ref, eacc, yg, dt):
+    """GanNormFuse forward: the finishing reduce takes mean / rstd / moving averages and out from y AS STORED (splitk_norm.h: the
+    arithmetic of reduce + stats_finalize + norm_act_fwd), so the reference is computed from the stored y - itself checked against
+    the fp64 convolution above - with the gates of those separate launches."""
+    res = {}
+    G = d.stats_groups
+    C_ = nf.out.c
+    y = yg[..., :C_]
+    m, var, dm, dvar, R = stats_gate(y, torch.zeros_like(y), G)
+    rs, drs = rstd_of(var, dvar, nf.eps)
+    gm = read(nf.mean, G * C_).double().reshape(G, C_)
+    gr = read(nf.rstd, G * C_).double().reshape(G, C_)
+    res['norm_fuse mean'] = ratio(gm, m, dm + 4 * EPS32 * m.abs())
+    res['norm_fuse rstd'] = ratio(gr, rs, drs)
+    if nf.moving_mean:
+        mm, mv = pre['mm'].clone(), pre['mv'].clone()
+        emm, emv = torch.zeros_like(mm), torch.zeros_like(mv)
+        adj = R / max(R - 1, 1)
+        k = 1.0 - nf.momentum
+        for g in range(G):                       # once per group, in order
+            mm = mm + (m[g] - mm) * k
+            mv = mv + (var[g] * adj - mv) * k
+            emm = emm * nf.momentum + k * dm[g] + 4 * EPS32 * (mm.abs() + m[g].abs())
+            emv = emv * nf.momentum + k * dvar[g] * adj + 4 * EPS32 * (mv.abs() + var[g].abs() * adj)
+        res['norm_fuse moving_mean'] = ratio(read(nf.moving_mean, C_).double(), mm, emm)
+        res['norm_fuse moving_var'] = ratio(read(nf.moving_var, C_).double(), mv, emv)
+    yg_ = grp(y, G)
+    xhat = (yg_ - m.unsqueeze(1)) * rs.unsqueeze(1)
+    gam, bet = pre['ngamma'], pre['nbeta']
+    z = xhat * gam + bet
+    ez = gam.abs() * (rs.unsqueeze(1) * dm.unsqueeze(1) + (yg_ - m.unsqueeze(1)).abs() * drs.unsqueeze(1)) \
+        + 4 * EPS32 * ((xhat * gam).abs() + bet.abs())
+    m2 = 2.0 * grp(pre['nmask'], G) if 'nmask' in pre else torch.ones_like(z)
+    out = act_f(z * m2, nf.act, nf.slope)
+    out1 = View(nf.out, dt)
+    got = grp(out1.dense(), G)
+    res['norm_fuse out'] = ratio(got, out, K_ULP * ulp(out, dt) + ez * m2)
+    res['norm_fuse out untouched outside c'] = untouched(out0, out1, 0, C_)
+    return res
+
+
+def check_wgrad(call):
+    d = call.args[0]._obj
+    dt = d.dtype
+    info = (C.c_int32 * 4)()
+    L.check(L.load().gan_wgrad_plan_info(C.byref(d), info), "wgrad_plan_info")
+    af = L.GanAdamFuse.from_address(d.adam_fuse) if d.adam_fuse else None
+    call.plan = f"wgrad tile {info[0]}x{info[1]} split {info[2]} fold {info[3]}" + (" adam_fuse" if af else "") + \
+        (" acc" if d.accumulate else "") + (f" conc{d.concurrent}" if d.concurrent else "")
+    if d.dw_wire:
+        raise AssertionError("dw_wire launches are out of the audit's scope (multi-rank)")
+    big, small = View(d.big, dt).dense(), View(d.small, dt).dense()
+    n = 16 * d.big_c * d.small_c
+    dw0 = read(d.dw, n)
+    if af is not None:
+        p0, m0, v0 = read(af.master, n).double(), read(af.m, n).double(), read(af.v, n).double()
+    yield
+    res = {}
+    g = wgrad_ref(big, small, d.stride, d.big_c, d.small_c).reshape(-1)
+    # sum|terms| <= max|big| * sum over positions of |small| per small channel (the cheap bound: an exact |big| x |small| pass would
+    # double the reference's cost)
+    sb = float(big[..., :d.big_c].abs().max()) * small[..., :d.small_c].abs().sum((0, 1, 2))
+    eg = ACC * sb.expand(16, d.big_c, d.small_c).reshape(-1)
+    dw1 = read(d.dw, n)
+    if af is None:
+        acc = float(d.accumulate)
+        ref = g + acc * dw0.double()
+        res['dw acc' if d.accumulate else 'dw'] = ratio(dw1, ref, eg + ACC * acc * dw0.double().abs() + ulp(ref, L.F32))
+        return res
+    res['dw untouched'] = 0.0 if torch.equal(dw0.view(torch.int32), dw1.view(torch.int32)) else math.inf
+    b1, b2 = af.beta1, af.beta2
+    m1, v1 = read(af.m, n).double(), read(af.v, n).double()
+    p1 = read(af.master, n).double()
+    mr = m0 + (g - m0) * (1 - b1)
+    vr = v0 + (g * g - v0) * (1 - b2)
+    res['adam m'] = ratio(m1, mr, (1 - b1) * eg + 4 * EPS32 * (m0.abs() + g.abs()))
+    res['adam v'] = ratio(v1, vr, (1 - b2) * (2 * g.abs() * eg + eg * eg) + 4 * EPS32 * (v0.abs() + g * g))
+    lr_t = float(read(af.lr_t, 1)[0])
+    step = lr_t * m1 / (torch.sqrt(v1) + af.eps)                       # TF-form Adam on the kernel's own new moments
+    pr = p0 - step
+    res['adam master'] = ratio(p1, pr, ulp(pr, L.F32) + 4 * EPS32 * step.abs())
+    p1f = read(af.master, n).reshape(16, d.big_c, d.small_c)
+    tdt = TDT[dt]
+    if af.nk_native:
+        sp = (d.small_c + 7) // 8 * 8
+        nat = read(af.nk_native, 16 * d.big_c * sp, dt).reshape(16, d.big_c, sp)[..., :d.small_c]
+        res['nk_native = cast(master)'] = 0.0 if torch.equal(nat, p1f.to(tdt)) else math.inf
+    if af.nk_transposed:
+        bp = (d.big_c + 7) // 8 * 8
+        tr = read(af.nk_transposed, 16 * d.small_c * bp, dt).reshape(16, d.small_c, bp)[..., :d.big_c]
+        res['nk_transposed = cast(master)'] = 0.0 if torch.equal(tr, p1f.transpose(1, 2).to(tdt)) else math.inf
+    return res
+
+
+def check_norm_stats(call):
+    """gan_norm_stats / gan_norm_stats_finalize(chunks: the conv epilogue's partials): mean, rstd, moving averages against the
+    statistics of the STORED y."""
+    d = call.args[0]._obj
+    dt, G, C_ = d.dtype, d.groups, d.y.c
+    fin = call.name == 'gan_norm_stats_finalize'
+    call.plan = f"groups {G}" + (f" chunks {call.args[1]}" if fin else "")
+    y = View(d.y, dt).dense()
+    mm0 = read(d.moving_mean, C_).double() if d.moving_mean else None
+    mv0 = read(d.moving_var, C_).double() if d.moving_var else None
+    yield
+    m, var, dm, dvar, R = stats_gate(y, torch.zeros_like(y), G)     # (a conv epilogue's partials are sums of the stored y too)
+    rs, drs = rstd_of(var, dvar, d.eps)
+    res = {'mean': ratio(read(d.mean, G * C_).double().reshape(G, C_), m, dm + 4 * EPS32 * m.abs()),
+           'rstd': ratio(read(d.rstd, G * C_).double().reshape(G, C_), rs, drs)}
+    if mm0 is not None:
+        k = 1.0 - d.momentum
+        adj = R / max(R - 1, 1)
+        emm, emv = torch.zeros_like(mm0), torch.zeros_like(mv0)
+        for g in range(G):
+            mm0 = mm0 + (m[g] - mm0) * k
+            mv0 = mv0 + (var[g] * adj - mv0) * k
+            emm = emm * d.momentum + k * dm[g] + 4 * EPS32 * (mm0.abs() + m[g].abs())
+            emv = emv * d.momentum + k * dvar[g] * adj + 4 * EPS32 * (mv0.abs() + var[g].abs() * adj)
+        res['moving_mean'] = ratio(read(d.moving_mean, C_).double(), mm0, emm)
+        res['moving_var'] = ratio(read(d.moving_var, C_).double(), mv0, emv)
+    return res
+
+
+def check_norm_act_fwd(call):
+    d = call.args[0]._obj
+    dt, G, C_ = d.dtype, d.groups, d.y.c
+    call.plan = f"groups {G} act {d.act}" + (" dropout" if d.dropmask else "")
+    y = View(d.y, dt).dense()
+    mean = read(d.mean, G * C_).double().reshape(G, C_)
+    rstd = read(d.rstd, G * C_).double().reshape(G, C_)
+    gam, bet = read(d.gamma, C_).double(), read(d.beta, C_).double()
+    mask = _mask(d.dropmask, d.y.n, d.y.h, d.y.w, C_, C_) if d.dropmask else None
+    a0 = View(d.a, dt)
+    yield
+    a1 = View(d.a, dt)
+    xh = (grp(y, G) - mean.unsqueeze(1)) * rstd.unsqueeze(1)
+    z = xh * gam + bet
+    m2 = 2.0 * grp(mask, G) if mask is not None else torch.ones_like(z)
+    out = act_f(z * m2, d.act, d.slope)
+    ez = 4 * EPS32 * ((xh * gam).abs() + bet.abs()) * m2
+    return {'a': ratio(grp(a1.dense(), G), out, K_ULP * ulp(out, dt) + ez), 'a untouched outside c': untouched(a0, a1, 0, d.a.c)}
+
+
+def check_norm_act_bwd(call):
+    """gan_norm_act_bwd (dz from da, da2, mask, act) and gan_norm_act_bwd_fused (da holds the stored dz, the workspace the
+    producing dgrad's partials): dy, dgamma, dbeta."""
+    d = call.args[0]._obj
+    dt, G, C_ = d.dtype, d.groups, d.y.c
+    fused = call.name == 'gan_norm_act_bwd_fused'
+    call.plan = f"groups {G}" + (f" fused chunks {call.args[1]}" if fused else f" act {d.act}" + (" dropout" if d.dropmask else ""))
+    y = View(d.y, dt).dense()
+    da = View(d.da, dt).dense()
+    da2 = View(d.da2, dt).dense() if d.da2.ptr else None
+    mean = read(d.mean, G * C_).double().reshape(G, C_)
+    rstd = read(d.rstd, G * C_).double().reshape(G, C_)
+    gam, bet = read(d.gamma, C_).double(), read(d.beta, C_).double()
+    mask = _mask(d.dropmask, d.y.n, d.y.h, d.y.w, C_, C_) if (d.dropmask and not fused) else None
+    dg0 = read(d.dgamma, C_).double() if d.dgamma else None
+    db0 = read(d.dbeta, C_).double() if d.dbeta else None
+    dy0 = View(d.dy, dt)
+    yield
+    res = {}
+    xh = (grp(y, G) - mean.unsqueeze(1)) * rstd.unsqueeze(1)
+    if fused:
+        dz = grp(da, G)
+        edz = 0.5 * ulp(dz, dt)                  # the producer's partials summed dz before its rounding to storage
+        dzs = dz                                 # the apply pass reads the stored dz
+    else:
+        g_ = da + da2 if da2 is not None else da
+        z = xh * gam + bet
+        zb = 8 * EPS32 * ((xh * gam).abs() + bet.abs()) + 1e-30
+        m2 = 2.0 * grp(mask, G) if mask is not None else torch.ones_like(z)
+        lo, hi = kink_d(z * m2, zb * m2, d.act, d.slope)
+        dz = grp(g_, G) * lo * m2
+        edz = (grp(g_, G) * (hi - lo) * m2).abs() + 4 * EPS32 * dz.abs()
+        dzs = dz
+    s1 = dz.mean(1, keepdim=True)
+    s2 = (dz * xh).mean(1, keepdim=True)
+    e1 = edz.mean(1, keepdim=True) + ACC * dz.abs().mean(1, keepdim=True)
+    e2 = (edz * xh.abs()).mean(1, keepdim=True) + ACC * (dz * xh).abs().mean(1, keepdim=True)
+    gr = (gam * rstd).unsqueeze(1)
+    ref = gr * (dzs - s1 - xh * s2)
+    gate = K_ULP * ulp(ref, dt) + gr.abs() * ((0 if fused else edz) + e1 + xh.abs() * e2) + \
+        4 * EPS32 * gr.abs() * (dzs.abs() + s1.abs() + (xh * s2).abs())
+    dy1 = View(d.dy, dt)
+    res['dy'] = ratio(grp(dy1.dense(), G), ref, gate)
+    res['dy untouched outside c'] = untouched(dy0, dy1, 0, d.dy.c)
+    if dg0 is not None:
+        acc = float(d.accumulate)
+        rg_ = (dz * xh).sum((0, 1)) + acc * dg0
+        rb_ = dz.sum((0, 1)) + acc * db0
+        res['dgamma'] = ratio(read(d.dgamma, C_).double(), rg_, (edz * xh.abs()).sum((0, 1)) + ACC * ((dz * xh).abs().sum((0, 1)) + acc * dg0.abs()))
+        res['dbeta'] = ratio(read(d.dbeta, C_).double(), rb_, edz.sum((0, 1)) + ACC * (dz.abs().sum((0, 1)) + acc * db0.abs()))
+    return res
+
+
+def check_act_bwd(call):
+    d = call.args[0]._obj
+    dt, C_ = d.dtype, d.dy.c
+    call.plan = f"act {d.act}" + (" dbias" if d.dbias else "")
+    a = View(d.a, dt).dense()
+    g_ = View(d.da, dt).dense()
+    if d.da2.ptr:
+        g_ = g_ + View(d.da2, dt).dense()
+    db0 = read(d.dbias, C_).double() if d.dbias else None
+    dy0 = View(d.dy, dt)
+    yield
+    lo, hi = kink_d(a, torch.zeros_like(a), d.act, d.slope)       # act'(a): a == 0 takes either side
+    rlo, rhi = torch.minimum(g_ * lo, g_ * hi), torch.maximum(g_ * lo, g_ * hi)
+    dy1 = View(d.dy, dt)
+    got = dy1.dense()
+    res = {'dy': between(got, rlo, rhi, K_ULP * ulp(rhi, dt) + 4 * EPS32 * rhi.abs()),
+           'dy untouched outside c': untouched(dy0, dy1, 0, C_)}
+    if db0 is not None:
+        acc = float(d.accumulate)
+        s = got.sum((0, 1, 2)) + acc * db0
+        res['dbias'] = ratio(read(d.dbias, C_).double(), s, ACC * (got.abs().sum((0, 1, 2)) + acc * db0.abs()))
+    return res
+
+
+def check_bias_grad(call):
+    dt, dyp, dbias, acc = call.args[0], call.args[1]._obj, call.args[2], call.args[3]
+    call.plan = "acc" if acc else ""
+    dy = View(dyp, dt).dense()
+    db0 = read(dbias, dyp.c).double()
+    yield
+    s = dy.sum((0, 1, 2)) + acc * db0
+    return {'dbias': ratio(read(dbias, dyp.c).double(), s, ACC * (dy.abs().sum((0, 1, 2)) + acc * db0.abs()))}
+
+
+CHECKERS = dict({k: check_conv for k in OPS}, gan_conv_wgrad=check_wgrad, gan_norm_stats=check_norm_stats,
+                gan_norm_stats_finalize=check_norm_stats, gan_norm_act_fwd=check_norm_act_fwd, gan_norm_act_bwd=check_norm_act_bwd,
+                gan_norm_act_bwd_fused=check_norm_act_bwd, gan_act_bwd=check_act_bwd, gan_bias_grad=check_bias_grad)
+
+
+def _short(sym):
+    m = re.match(r'_Z(?:N\d*)?(\d+)', sym)
+    if not m:
+        return sym
+    n = int(m.group(1))
+    return sym[m.end():m.end() + n]
+
+
+def replay(calls, stream=None):
+    """Re-issue the recorded calls in order on one stream, each checked against its reference.  Returns rows
+    (label, entry point, plan, kernels, {item: error/gate}) - None for allowlisted entry points."""
+    lib = L.load()
+    stream = stream or torch.cuda.current_stream()
+    st = stream.cuda_stream
+    rows = []
+    for c in calls:
+        chk = CHECKERS.get(c.name)
+        if chk is None and c.name not in ALLOWLIST:
+            raise AssertionError(f"{c.name} ({c.label}) has neither a reference in tests/launch_audit.py nor an ALLOWLIST entry")
+        torch.cuda.synchronize()
+        c.plan = ''
+        gen = chk(c) if chk is not None else None
+        if gen is not None:
+            next(gen)                                           # snapshot
+        L.check(lib.gan_set_option(b'diag.launch_log', 1), "launch log")
+        rc = c.fn(*c.args[:-1], st)
+        torch.cuda.synchronize()
+        syms = [_short(s) for s in L.launch_log()]
+        L.check(lib.gan_set_option(b'diag.launch_log', 0), "launch log")
+        if rc:
+            L.check(rc, f"{c.name} ({c.label})")
+        res = None
+        if gen is not None:
+            try:
+                next(gen)
+            except StopIteration as e:
+                res = e.value
+        rows.append((c.label, c.name, c.plan, ','.join(dict.fromkeys(syms)), res))
+    return rows
+
+
+def table(rows, title=''):
+    lines = [f"== launch audit {title}: {len(rows)} calls"]
+    for lab, name, plan, ks, res in rows:
+        if res is None:
+            lines.append(f"  {lab[:44]:44s} {name[4:]:22s} allowlisted")
+            continue
+        worst = max(res.items(), key=lambda kv: kv[1]) if res else ('-', 0.0)
+        lines.append(f"  {lab[:44]:44s} {name[4:]:22s} {plan:50s} {ks[:70]:70s} {worst[0]} {worst[1]:.3f}")
+    return '\n'.join(lines)
+
+
+def failures(rows):
+    return [(lab, name, plan, k, v) for lab, name, plan, ks, res in rows if res for k, v in res.items() if not v <= 1.0]
+
+
+def worst_per_entry(rows):
+    w = {}
+    for lab, name, plan, ks, res in rows:
+        if res:
+            v = max(res.values())
+            w[name] = max(w.get(name, 0.0), v)
+    return w
