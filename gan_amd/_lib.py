@@ -28,6 +28,12 @@ class GanPrepEntry(C.Structure):
                 ("B", C.c_int32), ("tile_start", C.c_int32), ("tiles_b", C.c_int32)]
 
 
+class GanFoldEntry(C.Structure):
+    _fields_ = [("master", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("moving_mean", C.c_void_p),
+                ("moving_var", C.c_void_p), ("bias", C.c_void_p), ("nk", C.c_void_p), ("A", C.c_int32), ("B", C.c_int32),
+                ("transposed", C.c_int32), ("tile_start", C.c_int32), ("tiles_k", C.c_int32)]
+
+
 class _Desc(C.Structure):
     """Descriptor structs carry their own size first (include/gan_amd.h): filled in here, so call sites list only the
     real fields; the library rejects a size it was not built with (GAN_E_ARG)."""
@@ -112,6 +118,7 @@ SYMBOLS = {
     "gan_wgrad_wire_direct": (C.c_int, [C.POINTER(GanWgradDesc)]),
     "gan_weights_prepare": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gan_weights_prepare_multi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "gan_bn_fold_multi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
     "gan_adam_prepare_multi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
     "gan_norm_stats": (C.c_int, [C.POINTER(GanNormDesc), C.c_void_p]),

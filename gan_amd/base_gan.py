@@ -2,9 +2,13 @@
 
 `Generator(...)` / `Discriminator(...)` return callable model objects (`model(x, training=True)`), like the
 Keras models of the reference; their weights live in `gan_amd.nets.ParamSet` buffers shared with the fused
-train-step objects.  As in the reference, `training=True` is what every call site uses (batch statistics,
-dropout on — pix2pix.py:200-203,228); the flag is accepted and ignored the same way Keras ignores it for
-layers without inference-time state in this graph."""
+train-step objects.  As in the reference, `training=True` is the default and what every call site of the
+training loop uses (batch statistics, dropout on, moving statistics updated — pix2pix.py:200-203,228).
+`training=False` is Keras inference mode: BatchNormalization normalises with its moving statistics and Dropout
+is the identity, so the output is deterministic and independent of the rest of the batch.  BatchNorm layers
+then run as one convolution each on weights folded with the moving statistics (gan_bn_fold_multi); the fold is
+refreshed on every such call, so it always reflects the current weights.  InstanceNorm has no inference-time
+state: for CycleGAN only the dropout differs."""
 from __future__ import annotations
 
 import ctypes as C
@@ -57,9 +61,11 @@ class GeneratorModel(_Model):
     layers = GEN_LAYERS
 
     def __init__(self, net: GeneratorNet, obj_name='generator'):
-        self.net, self.obj_name, self._calls = net, obj_name, {}
+        self.net, self.obj_name, self._calls, self._eval_calls = net, obj_name, {}, {}
 
     def __call__(self, x, training=True):
+        if not training:
+            return self.infer(x, fold=True)
         ctx = self.net.ctx
         x = _to_dev(x, ctx)
         B, S = x.shape[0], x.shape[1]
@@ -71,12 +77,31 @@ class GeneratorModel(_Model):
         call.forward()
         return call.output_f32()
 
+    def fold(self):
+        """Fold the current weights and moving statistics into the inference-mode weights (BatchNorm; nothing for InstanceNorm)."""
+        if self.net.norm == 'batchnorm':
+            self.net.folded().fold()
+
+    def infer(self, x, fold=True):
+        """`model(x, training=False)`.  fold=False: skip the fold launch - only right if fold() ran after the last change of the
+        weights or moving statistics (a train step, load_state_dict, a checkpoint restore)."""
+        ctx = self.net.ctx
+        x = _to_dev(x, ctx)
+        B, S = x.shape[0], x.shape[1]
+        key = (B, S)
+        if key not in self._eval_calls:
+            self._eval_calls[key] = self.net.new_eval_call(B, S)
+        call = self._eval_calls[key]
+        call.set_input(x)
+        call.infer(fold=fold)
+        return call.output_f32()
+
 
 class DiscriminatorModel(_Model):
     layers = DISC_LAYERS
 
     def __init__(self, net: DiscriminatorNet, obj_name='discriminator'):
-        self.net, self.obj_name, self._calls = net, obj_name, {}
+        self.net, self.obj_name, self._calls, self._eval_calls = net, obj_name, {}, {}
 
     def __call__(self, inputs, training=True):
         ctx = self.net.ctx
@@ -84,13 +109,17 @@ class DiscriminatorModel(_Model):
         xs = [_to_dev(x, ctx) for x in xs]
         B, S, Cc = xs[0].shape[0], xs[0].shape[1], self.net.channels
         key = (B, S)
-        if key not in self._calls:
-            self._calls[key] = self.net.new_call(B, S, calls=1)
-        call = self._calls[key]
+        calls = self._calls if training else self._eval_calls
+        if key not in calls:
+            calls[key] = self.net.new_call(B, S, calls=1) if training else self.net.new_eval_call(B, S)
+        call = calls[key]
         for i, x in enumerate(xs):      # concatenate([inp, tar]) realised as channel slices (base_gan.py:139)
             v = call.xin.view(i * Cc, Cc)
             L.check(ctx.lib.gan_pack(ctx.dt, x.data_ptr(), C.byref(v), ctx.stream()), "pack")
-        call.forward()
+        if training:
+            call.forward()
+        else:                           # inference mode: moving statistics (folded into the convolutions on every call)
+            call.infer(fold=True)
         return call.logits.t.clone()
 
 

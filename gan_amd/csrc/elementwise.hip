@@ -1,6 +1,6 @@
 // HBM-bound kernels of the training step other than normalisation (norm.hip): BCE-from-logits / L1 losses
-// with fused gradients, TF-form Adam, weight layout preparation, dropout-mask generation and
-// fp32<->typed packing.  Reductions are two-stage and deterministic, never atomics.
+// with fused gradients, TF-form Adam, weight layout preparation, BatchNorm folding for inference mode, dropout-mask
+// generation and fp32<->typed packing.  Reductions are two-stage and deterministic, never atomics.
 #include "common.h"
 #include <type_traits>
 
@@ -308,6 +308,94 @@ __global__ __launch_bounds__(256) void adam_prep_multi_kernel(const PrepEntry* e
   }
 }
 
+// Keras BatchNormalization in inference form folded into the bias-free convolution in front of it (gan_bn_fold_multi): per output
+// channel s = gamma * rsqrt(moving_variance + eps), bias = beta - moving_mean * s, and the NK weights the forward reads, rows
+// scaled by s.  One 64 (output channels) x 64 (input channels) tile of one tap of one kernel per block, written as rows of 8
+// channels (16-byte stores for the 16-bit types, two for fp32); pad8 columns are written as zeros.  The fp32 master is scaled
+// BEFORE the one rounding to T.  Contraction is off so that s, bias and every product are the plain IEEE fp32 results.
+struct FoldEntry {
+  const float* master; const float* gamma; const float* beta; const float* mean; const float* var;
+  float* bias; void* nk;
+  int32_t A, B, transposed, tile_start, tiles_k;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void bn_fold_multi_kernel(const FoldEntry* ents, int n, float eps) {
+#pragma clang fp contract(off)
+  __shared__ float tile[64][65];       // transposed entries: [input channel][output channel], already scaled
+  __shared__ float s_sh[64];
+  int e = 0;
+  while (e + 1 < n && (int)blockIdx.x >= ents[e + 1].tile_start) ++e;
+  const FoldEntry en = ents[e];
+  const int CO = en.transposed ? en.B : en.A, CI = en.transposed ? en.A : en.B;
+  const int K8 = (CI + 7) & ~7;
+  const int tiles_r = (CO + 63) / 64;
+  int t = (int)blockIdx.x - en.tile_start;
+  const int tk = t % en.tiles_k; t /= en.tiles_k;
+  const int tr = t % tiles_r, tap = t / tiles_r;
+  const int r0 = tr * 64, k0 = tk * 64;
+  if (tap >= 16) return;                        // (a total_tiles beyond the table's tiles: nothing to write)
+  const int tid = threadIdx.x;
+  if (tid < 64) {
+    const int co = r0 + tid;
+    float s = 0.f;
+    if (co < CO) {
+      const float rs = 1.0f / sqrtf(en.var[co] + eps);
+      s = en.gamma[co] * rs;
+      if (tap == 0 && tk == 0) {
+        const float ms = en.mean[co] * s;
+        en.bias[co] = en.beta[co] - ms;
+      }
+    }
+    s_sh[tid] = s;
+  }
+  __syncthreads();
+  T* nk = (T*)en.nk;
+  const int c8 = tid & 7, row = tid >> 3;       // 8 consecutive input channels of one output channel per thread, 32 rows per pass
+  if (en.transposed) {                          // Conv2D: HWIO master [tap][ci][co], coalesced along co, transposed through LDS
+    const int tx = tid & 63, ty = tid >> 6;
+    const int co = r0 + tx;
+    const float s = s_sh[tx];
+#pragma unroll 4
+    for (int i = 0; i < 16; ++i) {
+      const int ci = k0 + ty + 4 * i;
+      tile[ty + 4 * i][tx] = (ci < CI && co < CO) ? en.master[((size_t)tap * CI + ci) * CO + co] * s : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int rr = row + 32 * p, co2 = r0 + rr, ci0 = k0 + c8 * 8;
+      if (co2 < CO && ci0 < K8) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = tile[c8 * 8 + k][rr];
+        T* dst = nk + ((size_t)tap * CO + co2) * K8 + ci0;
+        if constexpr (sizeof(T) == 2) *(uint4*)dst = pack16<T>(v);
+        else { *(uint4*)dst = pack16<float>(v); *(uint4*)(dst + 4) = pack16<float>(v + 4); }
+      }
+    }
+  } else {                                      // Conv2DTranspose: (kh, kw, cout, cin) master [tap][co][ci], already in NK order
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int rr = row + 32 * p, co = r0 + rr, ci0 = k0 + c8 * 8;
+      if (co < CO && ci0 < K8) {
+        const float s = s_sh[rr];
+        const float* src = en.master + ((size_t)tap * CO + co) * CI + ci0;
+        float v[8];
+        if ((CI & 3) == 0 && ci0 + 8 <= CI) {   // 16-byte aligned rows (the master tensors start 256-byte aligned)
+          const float4 a = *(const float4*)src, b = *(const float4*)(src + 4);
+          v[0] = a.x * s; v[1] = a.y * s; v[2] = a.z * s; v[3] = a.w * s; v[4] = b.x * s; v[5] = b.y * s; v[6] = b.z * s; v[7] = b.w * s;
+        } else {                                // (pad8 columns: +0, not 0 * s)
+#pragma unroll
+          for (int k = 0; k < 8; ++k) v[k] = ci0 + k < CI ? src[k] * s : 0.f;
+        }
+        T* dst = nk + ((size_t)tap * CO + co) * K8 + ci0;
+        if constexpr (sizeof(T) == 2) *(uint4*)dst = pack16<T>(v);
+        else { *(uint4*)dst = pack16<float>(v); *(uint4*)(dst + 4) = pack16<float>(v + 4); }
+      }
+    }
+  }
+}
+
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -586,6 +674,17 @@ int gan_adam_prepare_multi(const void* entries_dev, int32_t n, int32_t total_til
     else
       GAN_LAUNCH((adam_prep_multi_kernel<T, false>), dim3((unsigned)total_tiles), dim3(256), 0, st, (const PrepEntry*)entries_dev, n, ab,
                          lr_t, 1.f - beta1, 1.f - beta2, eps, grad_scale, scale_state);
+    GAN_CHECK_LAUNCH();
+    return 0;
+  });
+}
+
+int gan_bn_fold_multi(const void* entries_dev, int32_t n, int32_t total_tiles, int32_t dtype, float eps, gan_stream_t stream) {
+  if (!entries_dev || n <= 0 || total_tiles <= 0 || !(eps > 0.f)) return GAN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  return with_dtype(dtype, [&](auto* tag) {
+    typedef GAN_TAG_T(tag) T;
+    GAN_LAUNCH(bn_fold_multi_kernel<T>, dim3((unsigned)total_tiles), dim3(256), 0, st, (const FoldEntry*)entries_dev, n, eps);
     GAN_CHECK_LAUNCH();
     return 0;
   });

@@ -163,10 +163,22 @@ class CycleGAN(GAN):
                           after_pass=(self.ctx.assert_no_stack_timeout if self.ctx.use_stacks else None))
 
     def predict(self, predict_ds, output_path: str):
+        """As Pix2Pix.predict: config['predict_training'] 'false' runs generator_g in inference mode (InstanceNorm has no
+        inference-time state: no dropout is the only difference) in batches of config['batch_size'] images."""
         plot_path = os.path.join(output_path, 'prediction_images')
         os.makedirs(plot_path)
-        for k, (img,) in enumerate(predict_ds.unbatch()):
-            self.generate_images(self.generator_g, img[None], os.path.join(plot_path, f"img{k}.png"))
+        if str(self.config.get('predict_training', 'true')) == 'true':
+            for k, (img,) in enumerate(predict_ds.unbatch()):
+                self.generate_images(self.generator_g, img[None], os.path.join(plot_path, f"img{k}.png"))
+            return
+        self.generator_g.fold()
+        k = 0
+        for chunk in D.chunked(predict_ds.unbatch(), int(self.config['batch_size'])):
+            pred = self.generator_g.infer(np.stack([img for (img,) in chunk]), fold=False).cpu().numpy()
+            for (img,), p in zip(chunk, pred):
+                save_panels(os.path.join(plot_path, f"img{k}.png"), [('Input Image', img), ('Predicted Image', p)],
+                            gray=self.config['channels'] == '1')
+                k += 1
 
 
 def parse_opt(argv=None):
@@ -195,6 +207,9 @@ def parse_opt(argv=None):
     parser.add_argument('--beta-2', type=float, default=0.999, help='exponential decay rate for 2st moment of Adam optimizer for generators and discriminators')
     parser.add_argument('--weights', type=str, help='path to pretrained model weights for prediction', required='--predict' in argv)
     parser.add_argument('--dtype', type=str, default='bf16', choices=['bf16', 'f16', 'f32'])
+    parser.add_argument('--predict-training', type=str, default='true', choices=['true', 'false'],
+                        help="--predict only: 'true' = the reference's generator(x, training=True) at batch 1 (batch statistics, "
+                             "dropout); 'false' = Keras inference mode (moving statistics, no dropout) in batches of --batch-size")
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')

@@ -143,3 +143,15 @@ class Batches:
     def unbatch(self):
         for f in self.files:
             yield self.make_example(f)
+
+
+def chunked(items, n):
+    """Consecutive lists of n items (the last one shorter if the items run out)."""
+    chunk = []
+    for it in items:
+        chunk.append(it)
+        if len(chunk) == n:
+            yield chunk
+            chunk = []
+    if chunk:
+        yield chunk

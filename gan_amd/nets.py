@@ -4,7 +4,8 @@ Follows the topology of the reference's builders (base_gan.py:63-225): `GAN.down
 `GAN.Generator`, `GAN.Discriminator`.  PyTorch is used only for device memory and streams; every
 arithmetic op is a hand-written HIP kernel reached through ctypes.  Each "call" object owns the
 activation / gradient buffers of ONE forward invocation of a network and a pre-built list of C calls, so
-running it is a plain loop of enqueue calls (capturable in a hipGraph).
+running it is a plain loop of enqueue calls (capturable in a hipGraph).  Inference calls (`new_eval_call`, `training=False`)
+own forward buffers only; their BatchNorm layers are single convolutions on weights folded with the moving statistics.
 
 Skip-concat (base_gan.py:219-221) is zero-copy: the up-layer's activation and the down-layer's
 activation are written by their producers straight into channel slices of one NHWC "cat" buffer.
@@ -726,11 +727,24 @@ class GeneratorNet:
         the guest call (host=that call) lives in those extra samples; host.backward(wgrads='wide') then covers both."""
         return GenCall(self, batch, size, dropout, seed, stream_id, wgrads_on_side_lane, lane, guest_batch, host)
 
+    def folded(self):
+        """The BatchNorm-folded weights of the inference calls (one set per network, shared by all of them; FoldedParams)."""
+        if self.__dict__.get('_folded') is None:
+            self._folded = FoldedParams(self.ctx, self.params, [(f'down{i}', True) for i in range(1, 8)] + [(f'up{j}', False) for j in range(7)])
+        return self._folded
+
+    def new_eval_call(self, batch, size, lane=0):
+        """`generator(x, training=False)`: forward-only call in inference mode (GenEvalCall for BatchNorm; for InstanceNorm, which
+        has no inference-time state, the training forward without dropout and without backward buffers)."""
+        if self.norm == 'batchnorm':
+            return GenEvalCall(self, batch, size, lane)
+        return GenCall(self, batch, size, False, 0, 0, lane=lane, forward_only=True)
+
 
 class GenCall:
     """Buffers + op lists for one invocation `generator(x, training=True)` and its backward."""
 
-    def __init__(self, net, B, S, dropout, seed, stream_id, wgrads_on_side_lane=False, lane=0, guest_batch=0, host=None):
+    def __init__(self, net, B, S, dropout, seed, stream_id, wgrads_on_side_lane=False, lane=0, guest_batch=0, host=None, forward_only=False):
         ctx, P = net.ctx, net.params
         self.net, self.ctx, self.B, self.S, self.C = net, ctx, B, S, net.channels
         self.guest_batch, self.host, self._pool, self._pool_i = int(guest_batch), host, [], 0
@@ -829,15 +843,17 @@ class GenCall:
         self.fwd_inner_start = len(head)
 
         # ---------------- backward ----------------
-        self.dcat = [Buf(ctx, B, hs[6 - j], hs[6 - j], G_UP[j] + G_DOWN[6 - j]) for j in range(7)]
-        self.da7 = Buf(ctx, B, hs[7], hs[7], 512)
-        self.dA = [Buf(ctx, B, hs[i], hs[i], G_DOWN[i]) for i in range(7)]     # grad wrt a_i from down i+1
-        self.dy_down = [Buf(ctx, B, hs[i], hs[i], G_DOWN[i]) for i in range(8)]
-        self.dy_up = [Buf(ctx, B, hs[6 - j], hs[6 - j], G_UP[j]) for j in range(7)]
-        self.dpre = Buf(ctx, B, S, S, 8)
-        self.dgen = Buf(ctx, B, S, S, 8)      # upstream gradient slot 1 (e.g. L1 term), channels [0, C)
-        self.dgen2 = Buf(ctx, B, S, S, 8)     # upstream gradient slot 2 (e.g. from the discriminator)
-        self.dxin = Buf(ctx, B, S, S, 8)
+        if not forward_only:      # (forward_only: an inference call, new_eval_call - no gradient storage)
+            self.dcat = [Buf(ctx, B, hs[6 - j], hs[6 - j], G_UP[j] + G_DOWN[6 - j]) for j in range(7)]
+            self.da7 = Buf(ctx, B, hs[7], hs[7], 512)
+            self.dA = [Buf(ctx, B, hs[i], hs[i], G_DOWN[i]) for i in range(7)]     # grad wrt a_i from down i+1
+            self.dy_down = [Buf(ctx, B, hs[i], hs[i], G_DOWN[i]) for i in range(8)]
+            self.dy_up = [Buf(ctx, B, hs[6 - j], hs[6 - j], G_UP[j]) for j in range(7)]
+            self.dpre = Buf(ctx, B, S, S, 8)
+            self.dgen = Buf(ctx, B, S, S, 8)      # upstream gradient slot 1 (e.g. L1 term), channels [0, C)
+            self.dgen2 = Buf(ctx, B, S, S, 8)     # upstream gradient slot 2 (e.g. from the discriminator)
+            self.dxin = Buf(ctx, B, S, S, 8)
+        self.fold_ops = []                        # (the inference-call surface of GenEvalCall: InstanceNorm has nothing to fold)
         self._bwd_cache = {}
         self.adam_fused = {}
         self.wire_direct = {}
@@ -1006,6 +1022,10 @@ class GenCall:
             inner_hook()
             self.ctx.run(self.fwd_ops[self.fwd_inner_start:])
 
+    def infer(self, fold=True):
+        """Inference-call surface (new_eval_call, InstanceNorm): the forward alone - no dropout, nothing to fold."""
+        self.ctx.run(self.fwd_ops)
+
     def out_view(self, n0=0, n=None):
         return self.out.view(0, self.C, n0, n)
 
@@ -1077,6 +1097,101 @@ class GenCall:
         return o
 
 
+class FoldedParams:
+    """Inference-mode weights of the BatchNorm layers of one network (gan_bn_fold_multi, include/gan_amd.h): per layer the NK
+    weights the forward reads, rows scaled by gamma * rsqrt(moving_variance + eps), and the bias beta - moving_mean * scale.
+    Buffers of their own: the NK copies and the master that the training step reads are never written here."""
+
+    def __init__(self, ctx, params, layers):
+        """layers: [(name, transposed)] - transposed: a Conv2D kernel (HWIO master; the forward reads ParamSet.tr), else a
+        Conv2DTranspose kernel ((kh,kw,cout,cin) master; the forward reads ParamSet.nat)."""
+        self.ctx = ctx
+        self.nk, self.bias = {}, {}
+        ents, tiles = [], 0
+        for name, transposed in layers:
+            o, shape = params.entries[name + '.kernel']
+            A, B = shape[2], shape[3]
+            co, ci = (B, A) if transposed else (A, B)
+            self.nk[name] = torch.zeros((16, co, pad8(ci)), dtype=ctx.tdtype, device=ctx.device)
+            self.bias[name] = torch.zeros(co, dtype=torch.float32, device=ctx.device)
+            tk = (pad8(ci) + 63) // 64
+            st = params.state
+            ents.append(L.GanFoldEntry(params.master.data_ptr() + 4 * o, params.ptr(name + '.gamma'), params.ptr(name + '.beta'),
+                                       st[name + '.moving_mean'].data_ptr(), st[name + '.moving_variance'].data_ptr(),
+                                       self.bias[name].data_ptr(), self.nk[name].data_ptr(), A, B, int(transposed), tiles, tk))
+            tiles += 16 * ((co + 63) // 64) * tk
+        arr = (L.GanFoldEntry * len(ents))(*ents)
+        self._table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(ctx.device)
+        self.fold_ops = [(ctx.lib.gan_bn_fold_multi, (self._table.data_ptr(), len(ents), tiles, ctx.dt, BN_EPS), "bn_fold_multi")]
+
+    def fold(self):
+        """Refresh the folded weights from the current master, gamma / beta and moving statistics (one launch)."""
+        self.ctx.run(self.fold_ops)
+
+
+class GenEvalCall:
+    """Buffers + op lists for one invocation `generator(x, training=False)` of a BatchNorm generator: Keras inference semantics
+    (moving statistics, no dropout).  Every BatchNorm layer is ONE convolution launch on folded weights with bias + activation in
+    its epilogue; forward buffers only.  fold_ops (the fold of every layer, one launch) + fwd_ops = ops; a caller whose weights
+    cannot change between calls runs fold_ops once."""
+
+    def __init__(self, net, B, S, lane=0):
+        ctx, P = net.ctx, net.params
+        if net.norm != 'batchnorm':
+            raise ValueError("GenEvalCall folds BatchNorm layers: use GeneratorNet.new_eval_call")
+        self.net, self.ctx, self.B, self.S, self.C = net, ctx, B, S, net.channels
+        bd = _Builder(ctx, P, net.norm, lane=lane)
+        self._bd = bd
+        C_ = net.channels
+        F = net.folded()
+        hs = [S >> (i + 1) for i in range(8)]
+        self.xin = Buf(ctx, B, S, S, 8)
+        self.out = Buf(ctx, B, S, S, 8)
+        self.cat = [Buf(ctx, B, hs[6 - j], hs[6 - j], G_UP[j] + G_DOWN[6 - j]) for j in range(7)]
+        self.a7 = Buf(ctx, B, hs[7], hs[7], 512)
+
+        def a_down(i):
+            if i == 7:
+                return self.a7.view()
+            j = 6 - i
+            return self.cat[j].view(G_UP[j], G_DOWN[i])
+        fwd = []
+        x = self.xin.view()
+        for i in range(8):
+            if i == 0:      # no normalisation (base_gan.py:180): as in training mode
+                fwd.append(bd.conv('conv_fwd', x, a_down(0), P.tr['down0.kernel'].data_ptr(), G_DOWN[0], 2, None, 'lrelu', k_real=C_))
+            else:           # Conv -> BN (moving statistics) -> LeakyReLU = conv on folded weights + bias + LeakyReLU
+                name = f'down{i}'
+                fwd.append(bd.conv('conv_fwd', x, a_down(i), F.nk[name].data_ptr(), G_DOWN[i], 2, F.bias[name].data_ptr(), 'lrelu'))
+            x = a_down(i)
+        for j in range(7):  # ConvT -> BN -> [Dropout: identity] -> ReLU, into the leading channels of the concat buffer
+            name = f'up{j}'
+            xin = self.a7.view() if j == 0 else self.cat[j - 1].view()
+            fwd.append(bd.conv('convT_fwd', xin, self.cat[j].view(0, G_UP[j]), F.nk[name].data_ptr(), G_UP[j], 2, F.bias[name].data_ptr(), 'relu'))
+        fwd.append(bd.conv('convT_fwd', self.cat[6].view(), self.out.view(0, C_), P.nat['last.kernel'].data_ptr(), C_, 2,
+                           P.ptr('last.bias'), 'tanh'))
+        self.fold_ops = F.fold_ops
+        self.fwd_ops = fwd
+        self.ops = self.fold_ops + self.fwd_ops
+
+    def set_input(self, x_f32):
+        dst = self.xin.view(0, self.C)
+        L.check(self.ctx.lib.gan_pack(self.ctx.dt, x_f32.data_ptr(), C.byref(dst), self.ctx.stream()), "pack")
+
+    def infer(self, fold=True):
+        """fold=False: the folded weights are current already (FoldedParams.fold since the last change of the weights)."""
+        self.ctx.run(self.ops if fold else self.fwd_ops)
+
+    def out_view(self, n0=0, n=None):
+        return self.out.view(0, self.C, n0, n)
+
+    def output_f32(self):
+        o = torch.empty((self.B, self.S, self.S, self.C), dtype=torch.float32, device=self.ctx.device)
+        v = self.out_view()
+        L.check(self.ctx.lib.gan_unpack(self.ctx.dt, C.byref(v), o.data_ptr(), self.ctx.stream()), "unpack")
+        return o
+
+
 class CallSlice:
     """A batch slice of a GenCall that stands for one logical generator invocation (masks, output, gradient slots)."""
 
@@ -1116,6 +1231,18 @@ class DiscriminatorNet:
         """lane / params_lane: whose workspace the forward + input-gradient chain / the parameter-gradient pass use."""
         return DiscCall(self, batch, size, calls, lane, params_lane)
 
+    def folded(self):
+        if self.__dict__.get('_folded') is None:
+            self._folded = FoldedParams(self.ctx, self.params, [('down1', True), ('down2', True), ('conv', True)])
+        return self._folded
+
+    def new_eval_call(self, batch, size, lane=0):
+        """`discriminator(x, training=False)`: one invocation, forward only (DiscEvalCall for BatchNorm; InstanceNorm: the training
+        forward without backward buffers)."""
+        if self.norm == 'batchnorm':
+            return DiscEvalCall(self, batch, size, lane)
+        return DiscCall(self, batch, size, 1, lane, forward_only=True)
+
 
 class DiscCall:
     """`calls` invocations of the discriminator batched along N (e.g. D(real) ++ D(fake), pix2pix.py:202-203);
@@ -1125,7 +1252,7 @@ class DiscCall:
 
     LAYERS = [('down0', 64, 2), ('down1', 128, 2), ('down2', 256, 2), ('conv', 512, 1), ('last', 1, 1)]
 
-    def __init__(self, net, B, S, calls, lane=0, params_lane=2):
+    def __init__(self, net, B, S, calls, lane=0, params_lane=2, forward_only=False):
         ctx, P = net.ctx, net.params
         self.net, self.ctx, self.B, self.S, self.calls = net, ctx, B, S, calls
         N = B * calls
@@ -1161,6 +1288,10 @@ class DiscCall:
         fwd.append(bd.conv('conv_fwd', prev.view(), self.logits.view(), P.tr['last.kernel'].data_ptr(), 1, 1,
                            P.ptr('last.bias'), None, 1))
         self.fwd_ops = merge_stacks(ctx, fwd)        # (runs start after down3: fwd_inner_start stays valid)
+        self.fold_ops = []
+        self._cache = {}
+        if forward_only:                             # an inference call (DiscriminatorNet.new_eval_call)
+            return
         # backward buffers (pass B reuses the first B samples' worth of them)
         self.dlogits = Buf(ctx, N, s5, s5, 8)        # pass A: all invocations (channel 0 real)
         self.dlogits_b = Buf(ctx, B, s5, s5, 8)      # pass B: one invocation
@@ -1172,6 +1303,9 @@ class DiscCall:
         self._cache = {}
 
     def forward(self):
+        self.ctx.run(self.fwd_ops)
+
+    def infer(self, fold=True):
         self.ctx.run(self.fwd_ops)
 
     def forward_part_ops(self, call, lane=0):
@@ -1297,3 +1431,38 @@ class DiscCall:
         if key not in self._cache:
             self._cache[key] = self._chain(call * self.B, self.B, self.gper, call * self.gper, False, True, False, dst, c0)
         self.ctx.run(self._cache[key])
+
+
+class DiscEvalCall:
+    """`discriminator(x, training=False)` of a BatchNorm PatchGAN: one invocation, BatchNorm with the moving statistics folded into
+    down1, down2 and conv (FoldedParams), forward buffers only.  Same surface as GenEvalCall (xin, fold_ops, fwd_ops, ops, infer)."""
+
+    def __init__(self, net, B, S, lane=0):
+        ctx, P = net.ctx, net.params
+        if net.norm != 'batchnorm':
+            raise ValueError("DiscEvalCall folds BatchNorm layers: use DiscriminatorNet.new_eval_call")
+        self.net, self.ctx, self.B, self.S = net, ctx, B, S
+        bd = _Builder(ctx, P, net.norm, lane=lane)
+        self._bd = bd
+        F = net.folded()
+        s1, s2, s3 = S // 2, S // 4, S // 8
+        s4, s5 = s3 - 1, s3 - 2
+        self.xin = Buf(ctx, B, S, S, 8)
+        self.a = {'down0': Buf(ctx, B, s1, s1, 64), 'down1': Buf(ctx, B, s2, s2, 128), 'down2': Buf(ctx, B, s3, s3, 256),
+                  'conv': Buf(ctx, B, s4, s4, 512)}
+        self.logits = Buf(ctx, B, s5, s5, 1, torch.float32)
+        fwd = [bd.conv('conv_fwd', self.xin.view(), self.a['down0'].view(), P.tr['down0.kernel'].data_ptr(), 64, 2, None, 'lrelu',
+                       k_real=net.cin)]
+        prev = 'down0'
+        for name, co, stride in DiscCall.LAYERS[1:4]:
+            fwd.append(bd.conv('conv_fwd', self.a[prev].view(), self.a[name].view(), F.nk[name].data_ptr(), co, stride,
+                               F.bias[name].data_ptr(), 'lrelu'))
+            prev = name
+        fwd.append(bd.conv('conv_fwd', self.a['conv'].view(), self.logits.view(), P.tr['last.kernel'].data_ptr(), 1, 1,
+                           P.ptr('last.bias'), None, 1))
+        self.fold_ops = F.fold_ops
+        self.fwd_ops = fwd
+        self.ops = self.fold_ops + self.fwd_ops
+
+    def infer(self, fold=True):
+        self.ctx.run(self.ops if fold else self.fwd_ops)

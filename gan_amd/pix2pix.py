@@ -165,10 +165,23 @@ class Pix2Pix(GAN):
                           after_pass=(self.ctx.assert_no_stack_timeout if self.ctx.use_stacks else None))
 
     def predict(self, predict_ds, output_path: str):
+        """config['predict_training'] 'true' (default): the reference's batch-1 `generator(x, training=True)` per image.  'false':
+        inference mode (moving statistics, no dropout), folded once - the weights stay fixed while predicting - and run in batches
+        of config['batch_size'] images; the same files in the same order."""
         plot_path = os.path.join(output_path, 'prediction_images')
         os.makedirs(plot_path, exist_ok=False)
-        for k, (inp, tar) in enumerate(predict_ds.unbatch()):
-            self.generate_images(self.generator, inp[None], tar[None], os.path.join(plot_path, f"img{k}.png"))
+        if str(self.config.get('predict_training', 'true')) == 'true':
+            for k, (inp, tar) in enumerate(predict_ds.unbatch()):
+                self.generate_images(self.generator, inp[None], tar[None], os.path.join(plot_path, f"img{k}.png"))
+            return
+        self.generator.fold()
+        k = 0
+        for chunk in D.chunked(predict_ds.unbatch(), int(self.config['batch_size'])):
+            pred = self.generator.infer(np.stack([inp for inp, _ in chunk]), fold=False).cpu().numpy()
+            for (inp, tar), p in zip(chunk, pred):
+                save_panels(os.path.join(plot_path, f"img{k}.png"), [('Input Image', inp), ('Ground Truth', tar), ('Predicted Image', p)],
+                            gray=self.config['channels'] == '1')
+                k += 1
 
 
 def parse_opt(argv=None):
@@ -198,6 +211,9 @@ def parse_opt(argv=None):
     parser.add_argument('--beta-2', type=float, default=0.999, help='exponential decay rate for 2st moment of Adam optimizer for generator and discriminator')
     parser.add_argument('--weights', type=str, help='path to pretrained model weights for prediction', required='--predict' in argv)
     parser.add_argument('--dtype', type=str, default='bf16', choices=['bf16', 'f16', 'f32'], help='MI355X compute/storage dtype (f32 = exact parity path)')
+    parser.add_argument('--predict-training', type=str, default='true', choices=['true', 'false'],
+                        help="--predict only: 'true' = the reference's generator(x, training=True) at batch 1 (batch statistics, "
+                             "dropout); 'false' = Keras inference mode (moving statistics, no dropout) in batches of --batch-size")
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')

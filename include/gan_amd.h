@@ -232,6 +232,32 @@ int gan_adam_prepare_multi(const void* entries_dev, int32_t n, int32_t total_til
                            float* v, const void* grad, const float* lr_t, float beta1, float beta2, float eps,
                            float grad_scale, const float* scale_state, int32_t grad_bf16, gan_stream_t stream);
 
+/* Inference mode (training=False): Keras BatchNormalization with its moving statistics (base_gan.py:83,113,151 called with
+ * training=False), y = gamma * (x - moving_mean) * rsqrt(moving_variance + eps) + beta, folded into the bias-free convolution
+ * in front of it (base_gan.py:77-79, :106-110, :145-148).  Per output channel co, in fp32 without contraction:
+ *     s[co] = gamma[co] * rsqrt(moving_var[co] + eps),   bias[co] = beta[co] - moving_mean[co] * s[co]
+ *     nk[tap][co][ci] = dtype(master(tap, co, ci) * s[co])        (pad8(Cin) columns written as zeros)
+ * so that the layer becomes ONE convolution launch with bias + activation in its epilogue.  `nk` has the layout the forward
+ * entry point reads, [16][Cout][pad8(Cin)]: transposed = 1 for a Conv2D (HWIO master [16][A = Cin][B = Cout], the
+ * gan_weights_prepare transposed copy), 0 for a Conv2DTranspose ((kh,kw,cout,cin) master [16][A = Cout][B = Cin], the native
+ * copy).  Writes only `bias` and `nk` (buffers of the caller's inference path: never the NK copies the training step reads);
+ * master, gamma, beta, moving_mean and moving_var are read only.  master and nk 16-byte aligned.
+ * tile_start = running sum of 16 * ceil(Cout/64) * tiles_k over the preceding entries, tiles_k = ceil(pad8(Cin)/64). */
+typedef struct GanFoldEntry {
+  const float* master;
+  const float* gamma;
+  const float* beta;
+  const float* moving_mean;
+  const float* moving_var;
+  float* bias;               /* [Cout] written */
+  void* nk;                  /* [16][Cout][pad8(Cin)] written, dtype */
+  int32_t A, B;              /* master dimensions, as GanPrepEntry */
+  int32_t transposed;
+  int32_t tile_start, tiles_k;
+} GanFoldEntry;
+/* Every BatchNorm-carrying kernel of a network in one launch (device array of n GanFoldEntry).  Enqueue-only, hipGraph-capturable. */
+int gan_bn_fold_multi(const void* entries_dev, int32_t n, int32_t total_tiles, int32_t dtype, float eps, gan_stream_t stream);
+
 /* ---- normalisation + activation ------------------------------------------------------------- */
 typedef struct GanNormDesc {
   uint32_t struct_size;  /* sizeof(GanNormDesc) of the caller's build */
