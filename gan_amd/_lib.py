@@ -97,6 +97,20 @@ class GanActBwdDesc(_Desc):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+AUGMENT_MAX_SAMPLES = 64
+
+
+class GanAugSample(C.Structure):
+    _fields_ = [("src_offset", C.c_int64), ("src_pitch", C.c_int32), ("col0", C.c_int32), ("col0_b", C.c_int32),
+                ("row_table", C.c_int32), ("col_table", C.c_int32), ("col_table_b", C.c_int32), ("crop_y", C.c_int32), ("crop_x", C.c_int32), ("flip", C.c_int32)]
+
+
+class GanAugmentDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("out", C.c_int32), ("c", C.c_int32), ("src", C.c_void_p),
+                ("src_bytes", C.c_int64), ("tables", C.c_void_p), ("n_tables", C.c_int32), ("table_len", C.c_int32),
+                ("lut", C.c_void_p), ("dst_a", C.c_void_p), ("dst_b", C.c_void_p), ("samples", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/gan_amd.h declares
 SYMBOLS = {
     "gan_conv2d_fwd": (C.c_int, [C.POINTER(GanConvDesc), C.c_void_p]),
@@ -154,6 +168,7 @@ SYMBOLS = {
     "gan_bias_grad": (C.c_int, [C.c_int32, C.POINTER(GanTensor), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gan_grad_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gan_grad_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    "gan_augment_u8": (C.c_int, [C.POINTER(GanAugmentDesc), C.c_void_p]),
     "gan_crc32c": (C.c_uint32, [C.c_uint32, C.c_void_p, C.c_size_t]),
     "gan_version": (C.c_char_p, []),
     "gan_set_option": (C.c_int, [C.c_char_p, C.c_int32]),

@@ -493,6 +493,74 @@ __global__ __launch_bounds__(256) void copy_view_kernel(const T* src, int spitch
   dst[(i / C) * dpitch + (i % C)] = src[(i / C) * spitch + (i % C)];
 }
 
+// ---- device-resident input pipeline (include/gan_amd.h: gan_augment_u8) ---------------------------------------------------------
+// A workgroup owns AUG_ROWS output rows of one sample (blockIdx.y) of one of the two tensors (blockIdx.z).  The columns a cropped
+// output row needs form one contiguous segment of the source row (the column table is non-decreasing): the workgroup stages that
+// segment of its AUG_ROWS source rows in LDS with aligned 16-byte loads, beside the 1-KB value table and the per-output-column
+// byte offsets (crop and mirror applied once), then every lane gathers from LDS and writes 16-byte stores.  A segment wider than
+// AUG_SEG bytes (or a table that is not monotone) gathers from global memory instead.  The per-sample parameters arrive by value in
+// the kernel arguments.  Every global read is clamped into [0, src_bytes); the grid covers dst exactly.
+constexpr int AUG_ROWS = 4, AUG_SEG = 4096, AUG_VEC = AUG_SEG / 16 + 2;
+struct AugArgs {
+  const uint8_t* src; long long src_bytes; const int32_t* tables; const float* lut; float* dst[2]; int table_len, out;
+  GanAugSample s[GAN_AUGMENT_MAX_SAMPLES];
+};
+template <int C>
+__global__ __launch_bounds__(256) void augment_u8_kernel(const AugArgs a) {
+  __shared__ float s_lut[256];
+  __shared__ int s_col[512];
+  __shared__ uint4 s_row[AUG_ROWS][AUG_VEC];
+  const GanAugSample& s = a.s[blockIdx.y];
+  const int tid = threadIdx.x, out = a.out, r0 = blockIdx.x * AUG_ROWS;
+  const int32_t* __restrict__ cols = a.tables + (long long)(blockIdx.z ? s.col_table_b : s.col_table) * a.table_len + s.crop_x;
+  const int32_t* __restrict__ rows = a.tables + (long long)s.row_table * a.table_len + s.crop_y + r0;
+  const int lo = cols[0], seg = (cols[out - 1] - lo + 1) * C;
+  const bool staged = seg > 0 && seg <= AUG_SEG;
+  s_lut[tid] = a.lut[tid];
+  for (int x = tid; x < out; x += 256) {
+    const int rel = (cols[s.flip ? out - 1 - x : x] - lo) * C;
+    s_col[x] = staged ? min(max(rel, 0), seg - C) : rel;
+  }
+  long long base[AUG_ROWS];      // byte offset in src of the segment's first byte, per row
+#pragma unroll
+  for (int r = 0; r < AUG_ROWS; ++r)
+    base[r] = s.src_offset + (long long)rows[r] * s.src_pitch + (long long)((blockIdx.z ? s.col0_b : s.col0) + lo) * C;
+  if (staged) {
+#pragma unroll
+    for (int r = 0; r < AUG_ROWS; ++r) {
+      const long long al = base[r] & ~15LL;
+      const int nvec = ((int)(base[r] - al) + seg + 15) >> 4;
+      for (int i = tid; i < nvec; i += 256) {
+        const long long at = min(max(al + 16LL * i, 0LL), a.src_bytes - 16);
+        s_row[r][i] = *(const uint4*)(a.src + at);
+      }
+    }
+  }
+  __syncthreads();
+  float* __restrict__ dst = a.dst[blockIdx.z] + ((long long)blockIdx.y * out + r0) * out * C;
+  for (int q = tid; q < out * C / 4; q += 256) {
+    int off[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int el = 4 * q + j, px = el / C;
+      off[j] = s_col[px] + (el - px * C);
+    }
+#pragma unroll
+    for (int r = 0; r < AUG_ROWS; ++r) {
+      float v[4];
+      if (staged) {
+        const uint8_t* rowp = (const uint8_t*)s_row[r] + (int)(base[r] & 15);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = s_lut[rowp[off[j]]];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = s_lut[a.src[min(max(base[r] + off[j], 0LL), a.src_bytes - 1)]];
+      }
+      *(float4*)(dst + (long long)r * out * C + 4 * q) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  }
+}
+
 // run f with a null pointer of the storage type as its tag
 template <typename F> static inline int with_dtype(int dtype, F&& f) {
   if (dtype == GAN_F32) return f((float*)nullptr);
@@ -772,6 +840,37 @@ int gan_copy_view(int32_t dtype, const GanTensor* src, const GanTensor* dst, gan
     GAN_CHECK_LAUNCH();
     return 0;
   });
+}
+
+int gan_augment_u8(const GanAugmentDesc* d, gan_stream_t stream) {
+  if (!d || d->struct_size != sizeof(GanAugmentDesc)) return GAN_E_ARG;
+  if (!d->src || !d->tables || !d->lut || !d->dst_a || !d->samples) return GAN_E_ARG;
+  if (d->n <= 0 || d->n > GAN_AUGMENT_MAX_SAMPLES || (d->c != 1 && d->c != 3) || d->n_tables <= 0) return GAN_E_ARG;
+  if (d->src_bytes < 16 || d->src_bytes % 16 || ((uintptr_t)d->src & 15) || ((uintptr_t)d->dst_a & 15) || ((uintptr_t)d->dst_b & 15))
+    return GAN_E_ARG;
+  if ((d->out != 256 && d->out != 512) || d->table_len < d->out) return GAN_E_SHAPE;
+  AugArgs a;
+  a.src = d->src; a.src_bytes = d->src_bytes; a.tables = d->tables; a.lut = d->lut; a.dst[0] = d->dst_a; a.dst[1] = d->dst_b;
+  a.table_len = d->table_len; a.out = d->out;
+  for (int i = 0; i < d->n; ++i) {
+    const GanAugSample& s = d->samples[i];
+    if (s.row_table < 0 || s.row_table >= d->n_tables || s.col_table < 0 || s.col_table >= d->n_tables ||
+        (d->dst_b && (s.col_table_b < 0 || s.col_table_b >= d->n_tables)))
+      return GAN_E_ARG;
+    if (s.src_offset < 0 || s.src_pitch <= 0 || s.src_offset + s.src_pitch > d->src_bytes || s.col0 < 0 || s.col0_b < 0 ||
+        (s.flip != 0 && s.flip != 1))
+      return GAN_E_ARG;
+    if (s.crop_y < 0 || s.crop_x < 0 || s.crop_y > d->table_len - d->out || s.crop_x > d->table_len - d->out) return GAN_E_SHAPE;
+    a.s[i] = s;
+  }
+  for (int i = d->n; i < GAN_AUGMENT_MAX_SAMPLES; ++i) a.s[i] = a.s[0];
+  const dim3 grid((unsigned)(d->out / AUG_ROWS), (unsigned)d->n, d->dst_b ? 2u : 1u);
+  if (d->c == 1)
+    GAN_LAUNCH(augment_u8_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else
+    GAN_LAUNCH(augment_u8_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  GAN_CHECK_LAUNCH();
+  return 0;
 }
 
 int gan_sum3(const float* a, const float* b, const float* c, float* out, int32_t n, gan_stream_t stream) {

@@ -84,6 +84,16 @@ class CycleGAN(GAN):
         train_Y = [i for i in cy if i not in val_Y]
         train_X, train_Y, val_X, val_Y = (ddp.shard_files(f, self.dist.rank, self.dist.world) for f in (train_X, train_Y, val_X, val_Y))
         bs, dev, sd = self.config["batch_size"], self.ctx.device, self.config['seed']
+        if self.config.get('data_cache', 'host') == 'device':        # decoded once, augmented by gan_augment_u8
+            cap = int(float(self.config.get('data_cache_gb', 64)) * 2**30)
+            ds = lambda files, jitter: D.DeviceDataset(files, int(self.config['channels']), self.config['img_size'], dev, 'single', jitter,
+                                                       cap_bytes=cap)
+            draw = lambda: D.draw_jitter(self._rng)      # in the consuming thread, X before Y per batch: reproducible run to run
+            return (D.DeviceBatches(ds(fx(train_X), True), bs, draw, sd, self.process_images_train),
+                    D.DeviceBatches(ds(fy(train_Y), True), bs, draw, sd + 1, self.process_images_train),
+                    D.DeviceBatches(ds(fx(val_X), False), bs, None, sd + 2, self.process_images_pred),
+                    D.DeviceBatches(ds(fy(val_Y), False), bs, None, sd + 3, self.process_images_pred),
+                    D.DeviceBatches(ds(fx(test), False), bs, None, None, self.process_images_pred))
         return (D.Batches(fx(train_X), self.process_images_train, bs, dev, shuffle_seed=sd),
                 D.Batches(fy(train_Y), self.process_images_train, bs, dev, shuffle_seed=sd + 1),
                 D.Batches(fx(val_X), self.process_images_pred, bs, dev, shuffle_seed=sd + 2),
@@ -210,6 +220,10 @@ def parse_opt(argv=None):
     parser.add_argument('--predict-training', type=str, default='true', choices=['true', 'false'],
                         help="--predict only: 'true' = the reference's generator(x, training=True) at batch 1 (batch statistics, "
                              "dropout); 'false' = Keras inference mode (moving statistics, no dropout) in batches of --batch-size")
+    parser.add_argument('--data-cache', type=str, default='host', choices=['host', 'device'],
+                        help="--train: 'host' decodes and augments every image on the CPU in every epoch; 'device' decodes each file once, "
+                             "keeps the uint8 images in GPU memory and builds every batch there")
+    parser.add_argument('--data-cache-gb', type=float, default=64, help='--data-cache device: most GiB of decoded images to keep per GPU')
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')

@@ -93,6 +93,13 @@ class Pix2Pix(GAN):
         train, val, test = D.pix2pix_split(contents, self.config['seed'], self.config['test_img'], self.config['validation_size'])
         train, val = (ddp.shard_files(f, self.dist.rank, self.dist.world) for f in (train, val))     # (every rank made the same split)
         bs = self.config["batch_size"]
+        if self.config.get('data_cache', 'host') == 'device':        # decoded once, augmented by gan_augment_u8
+            cap = int(float(self.config.get('data_cache_gb', 64)) * 2**30)
+            ds = lambda files, jitter: D.DeviceDataset(full(files), int(self.config['channels']), self.config['img_size'], dev, 'pair',
+                                                       jitter, self.config['input_img_orient'], cap)
+            return (D.DeviceBatches(ds(train, True), bs, lambda: D.draw_jitter(self._rng), make_example=self.process_images_train),
+                    D.DeviceBatches(ds(val, False), bs, make_example=self.process_images_pred),
+                    D.DeviceBatches(ds(test, False), bs, make_example=self.process_images_pred))
         return (D.Batches(full(train), self.process_images_train, bs, dev),
                 D.Batches(full(val), self.process_images_pred, bs, dev),
                 D.Batches(full(test), self.process_images_pred, bs, dev))
@@ -214,6 +221,10 @@ def parse_opt(argv=None):
     parser.add_argument('--predict-training', type=str, default='true', choices=['true', 'false'],
                         help="--predict only: 'true' = the reference's generator(x, training=True) at batch 1 (batch statistics, "
                              "dropout); 'false' = Keras inference mode (moving statistics, no dropout) in batches of --batch-size")
+    parser.add_argument('--data-cache', type=str, default='host', choices=['host', 'device'],
+                        help="--train: 'host' decodes and augments every image on the CPU in every epoch; 'device' decodes each file once, "
+                             "keeps the uint8 images in GPU memory and builds every batch there (identical batches)")
+    parser.add_argument('--data-cache-gb', type=float, default=64, help='--data-cache device: most GiB of decoded images to keep per GPU')
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')

@@ -424,6 +424,53 @@ int gan_bias_grad(int32_t dtype, const GanTensor* dy, float* dbias, int32_t accu
  * before the RCCL all-reduce, and back (times `scale` = 1/world) before Adam.  count % 8 == 0, 16-byte aligned. */
 int gan_grad_pack(const float* src, void* dst_bf16, int64_t count, gan_stream_t stream);
 int gan_grad_unpack(const void* src_bf16, float* dst, int64_t count, float scale, gan_stream_t stream);
+
+/* ---- device-resident input pipeline ------------------------------------------------------------ */
+/* The reference's tf.data map after the decode (pix2pix.py:34-87 / cycle_gan.py:40-72, base_gan.py:46-61: left/right split,
+ * nearest-neighbour resize to size+30, random crop, random mirror, v / 127.5 - 1), for uint8 images that stay in device memory:
+ * an integer gather through host-built index tables plus one 256-entry value table.
+ *     dst[i][r][x][ch] = lut[ src[src_offset + rows[crop_y + r] * src_pitch + (col0 + cols[crop_x + x']) * c + ch] ],
+ *     x' = flip ? out - 1 - x : x,   rows = tables + row_table * table_len,   cols = tables + col_table * table_len
+ * One GanAugSample per output image, in a HOST array that is read at call time (nothing of it has to outlive the call; no
+ * per-step upload).  dst_b (optional) is a second tensor of the same shape built from the same rows, crop and mirror but from
+ * the columns col0_b + (table col_table_b): both images of a Pix2Pix pair in one launch.  The table entries are trusted to lie inside
+ * the image (the caller built them from its size); every read is additionally clamped to [0, src_bytes). */
+typedef struct GanAugSample {
+  int64_t src_offset;  /* byte offset of the image's first pixel in src */
+  int32_t src_pitch;   /* bytes between consecutive source rows */
+  int32_t col0;        /* first source column (pixels) of the part that goes to dst_a; the split: 0 or width / 2 */
+  int32_t col0_b;      /* the same for dst_b (unused without dst_b) */
+  int32_t row_table;   /* table number of the row map, 0 <= . < n_tables */
+  int32_t col_table;   /* table number of the column map of dst_a */
+  int32_t col_table_b; /* the same for dst_b: the halves of an odd-width pair differ by one column (unused without dst_b) */
+  int32_t crop_y;      /* crop origin in the table: 0 <= crop_y <= table_len - out */
+  int32_t crop_x;
+  int32_t flip;        /* 1: mirrored left-right */
+} GanAugSample;
+
+enum { GAN_AUGMENT_MAX_SAMPLES = 64 };
+
+typedef struct GanAugmentDesc {
+  uint32_t struct_size;
+  int32_t n;                   /* samples of this launch, 1 ..= GAN_AUGMENT_MAX_SAMPLES */
+  int32_t out;                 /* output height = width: 256 or 512 */
+  int32_t c;                   /* channels, interleaved in the source: 1 or 3 */
+  const uint8_t* src;          /* device: the packed uint8 images; 16-byte aligned */
+  int64_t src_bytes;           /* size of that buffer, a multiple of 16 */
+  const int32_t* tables;       /* device: n_tables index tables of table_len entries each */
+  int32_t n_tables;
+  int32_t table_len;           /* out + 30 for the jittered form, out for the plain resize (validation, test) */
+  const float* lut;            /* device: 256 fp32 values, the normalised value of every byte */
+  float* dst_a;                /* device: dense fp32 [n, out, out, c], 16-byte aligned */
+  float* dst_b;                /* the pair's second tensor, or NULL */
+  const GanAugSample* samples; /* HOST array of n entries */
+} GanAugmentDesc;
+
+/* GAN_E_ARG: NULL pointer, wrong struct_size, n out of range, c not 1 or 3, misaligned buffer, table number out of range,
+ * source offset / pitch outside src.  GAN_E_SHAPE: out not 256 or 512, table_len < out, crop origin outside the table.  All of
+ * them are found before anything is launched. */
+int gan_augment_u8(const GanAugmentDesc* d, gan_stream_t stream);
+
 /* Host utility (no GPU): CRC-32C of TensorFlow's TensorBundle checkpoint files (tf.train.Checkpoint /
  * CheckpointManager, pix2pix.py:400-403,419-420; cycle_gan.py:437-444,460-461).  crc = 0 to start; chainable. */
 uint32_t gan_crc32c(uint32_t crc, const void* data, size_t n);
