@@ -111,6 +111,11 @@ class GanAugmentDesc(_Desc):
                 ("lut", C.c_void_p), ("dst_a", C.c_void_p), ("dst_b", C.c_void_p), ("samples", C.c_void_p)]
 
 
+class GanQualityDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("dtype_a", C.c_int32), ("dtype_b", C.c_int32), ("a", GanTensor), ("b", GanTensor),
+                ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 # name -> (restype, argtypes); every symbol include/gan_amd.h declares
 SYMBOLS = {
     "gan_conv2d_fwd": (C.c_int, [C.POINTER(GanConvDesc), C.c_void_p]),
@@ -169,6 +174,8 @@ SYMBOLS = {
     "gan_grad_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gan_grad_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "gan_augment_u8": (C.c_int, [C.POINTER(GanAugmentDesc), C.c_void_p]),
+    "gan_image_quality_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gan_image_quality": (C.c_int, [C.POINTER(GanQualityDesc), C.c_void_p]),
     "gan_crc32c": (C.c_uint32, [C.c_uint32, C.c_void_p, C.c_size_t]),
     "gan_version": (C.c_char_p, []),
     "gan_set_option": (C.c_int, [C.c_char_p, C.c_int32]),

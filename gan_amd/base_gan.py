@@ -85,6 +85,11 @@ class GeneratorModel(_Model):
     def infer(self, x, fold=True):
         """`model(x, training=False)`.  fold=False: skip the fold launch - only right if fold() ran after the last change of the
         weights or moving statistics (a train step, load_state_dict, a checkpoint restore)."""
+        return self.infer_call(x, fold).output_f32()
+
+    def infer_call(self, x, fold=True):
+        """infer() up to the forward: -> the eval call, whose typed output view (out_view()) holds the prediction until the next
+        call of this batch size (gan_amd.quality reads it there, without the unpack)."""
         ctx = self.net.ctx
         x = _to_dev(x, ctx)
         B, S = x.shape[0], x.shape[1]
@@ -94,7 +99,7 @@ class GeneratorModel(_Model):
         call = self._eval_calls[key]
         call.set_input(x)
         call.infer(fold=fold)
-        return call.output_f32()
+        return call
 
 
 class DiscriminatorModel(_Model):

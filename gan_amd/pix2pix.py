@@ -14,6 +14,7 @@ from . import data as D
 from . import ddp
 from .base_gan import GAN
 from .checkpoint import Checkpoint, CheckpointManager, latest_checkpoint
+from .quality import QualityMeter, image_quality, summary
 from .steps import Pix2PixStep
 from .runner import Run, plot_loss_curves, run_epochs, save_panels
 from .utils import pix2pix_losses
@@ -146,12 +147,38 @@ class Pix2Pix(GAN):
         return losses[0], losses[1], losses[2], losses[3]
 
     # ---- images / loops (pix2pix.py:220-339) -----------------------------------------------------
-    def generate_images(self, model, test_input, tar, path_filename: str):
-        """Input | ground truth | `model(test_input, training=True)` (batch statistics and dropout on, pix2pix.py:228)."""
-        pred = model(test_input, training=True).cpu().numpy()
+    def generate_images(self, model, test_input, tar, path_filename: str, quality=None):
+        """Input | ground truth | `model(test_input, training=True)` (batch statistics and dropout on, pix2pix.py:228).
+        quality: a QualityMeter that receives the metrics of this very prediction against `tar`."""
+        pred = model(test_input, training=True)
+        if quality is not None:
+            quality.add(image_quality(self.ctx, pred, tar))
+        pred = pred.cpu().numpy()
         host = lambda t: np.asarray(torch.as_tensor(t).cpu())
         save_panels(path_filename, [('Input Image', host(test_input)[0]), ('Ground Truth', host(tar)[0]), ('Predicted Image', pred[0])],
                     gray=self.config['channels'] == '1')
+
+    def _evaluate_into(self, meter, ds, training=False):
+        """Enqueue the predictions and the metrics of every batch of `ds` (no host sync)."""
+        if training:            # the reference's batch-1 generator(x, training=True): batch statistics, dropout
+            for x, y in ds:
+                x, y = torch.as_tensor(x), torch.as_tensor(y)
+                for k in range(x.shape[0]):
+                    meter.add(image_quality(self.ctx, self.generator(x[k:k + 1], training=True), y[k:k + 1]))
+            return
+        self.generator.fold()   # once: the weights stand still during the pass
+        for x, y in ds:
+            call = self.generator.infer_call(x, fold=False)
+            meter.add(image_quality(self.ctx, call.out_view(), y))      # the typed output view: no unpack
+
+    def evaluate(self, ds, training: bool = False):
+        """Image quality of the generator over a dataset of (input, target) batches (gan_amd/quality.py):
+        -> {'SSIM': [...], 'PSNR': [...], 'MAE': [...], 'MSE': [...]}, one entry per image in file order.  training=False:
+        inference mode, folded once, in the dataset's batches; training=True: the call `generate_images` makes, one image at a
+        time.  An inference forward writes no state: training is unchanged by it, bit for bit."""
+        meter = QualityMeter()
+        self._evaluate_into(meter, ds, training)
+        return meter.drain()
 
     def fit(self, train_ds, val_ds, test_ds, output_path: str, checkpoint_manager=None):
         print("\nTraining...\n", flush=True)
@@ -166,29 +193,47 @@ class Pix2Pix(GAN):
                                                     os.path.join(samples, f"epoch_{epoch}.png"))
         if not self.dist.is_main:           # rank 0 alone writes checkpoints and sample images
             save = sample = (lambda *a: None)
+        self.val_quality = {'SSIM': [], 'PSNR': [], 'MAE': []}
+        after_epoch = None
+        if str(self.config.get('quality_metrics', 'false')) == 'true':
+            def after_epoch(epoch):     # validation set in inference mode; epoch means over all ranks' images, as the losses
+                meter = QualityMeter()
+                self._evaluate_into(meter, val_ds)
+                mean = ddp.mean_over_ranks(*meter.sums(), self.dist)
+                vals = mean.cpu().tolist() if mean is not None else [float('nan')] * 4
+                for k, v in zip(self.val_quality, vals):
+                    self.val_quality[k].append(v)
+                return f"val SSIM: {vals[0]:.4f}, PSNR: {vals[1]:.2f} dB, MAE: {vals[2]:.4f}"
         return run_epochs(self.config['epochs'], list(pix2pix_losses()), lambda: train_ds, lambda: val_ds, self.train_step,
                           save, sample, ('Generator Total Loss', 'Discriminator Loss'),
                           epoch_mean=lambda acc, n: ddp.mean_over_ranks(acc, n, self.dist),
-                          after_pass=(self.ctx.assert_no_stack_timeout if self.ctx.use_stacks else None))
+                          after_pass=(self.ctx.assert_no_stack_timeout if self.ctx.use_stacks else None), after_epoch=after_epoch)
 
     def predict(self, predict_ds, output_path: str):
         """config['predict_training'] 'true' (default): the reference's batch-1 `generator(x, training=True)` per image.  'false':
         inference mode (moving statistics, no dropout), folded once - the weights stay fixed while predicting - and run in batches
-        of config['batch_size'] images; the same files in the same order."""
+        of config['batch_size'] images; the same files in the same order.
+        config['quality_metrics'] 'true': -> the image-quality metrics of the very predictions that are written as images, per
+        image in file order (Pix2Pix.evaluate's layout); otherwise None."""
         plot_path = os.path.join(output_path, 'prediction_images')
         os.makedirs(plot_path, exist_ok=False)
+        meter = QualityMeter() if str(self.config.get('quality_metrics', 'false')) == 'true' else None
         if str(self.config.get('predict_training', 'true')) == 'true':
             for k, (inp, tar) in enumerate(predict_ds.unbatch()):
-                self.generate_images(self.generator, inp[None], tar[None], os.path.join(plot_path, f"img{k}.png"))
-            return
+                self.generate_images(self.generator, inp[None], tar[None], os.path.join(plot_path, f"img{k}.png"), quality=meter)
+            return meter.drain() if meter is not None else None
         self.generator.fold()
         k = 0
         for chunk in D.chunked(predict_ds.unbatch(), int(self.config['batch_size'])):
-            pred = self.generator.infer(np.stack([inp for inp, _ in chunk]), fold=False).cpu().numpy()
+            pred = self.generator.infer(np.stack([inp for inp, _ in chunk]), fold=False)
+            if meter is not None:
+                meter.add(image_quality(self.ctx, pred, np.stack([tar for _, tar in chunk])))
+            pred = pred.cpu().numpy()
             for (inp, tar), p in zip(chunk, pred):
                 save_panels(os.path.join(plot_path, f"img{k}.png"), [('Input Image', inp), ('Ground Truth', tar), ('Predicted Image', p)],
                             gray=self.config['channels'] == '1')
                 k += 1
+        return meter.drain() if meter is not None else None
 
 
 def parse_opt(argv=None):
@@ -225,6 +270,10 @@ def parse_opt(argv=None):
                         help="--train: 'host' decodes and augments every image on the CPU in every epoch; 'device' decodes each file once, "
                              "keeps the uint8 images in GPU memory and builds every batch there (identical batches)")
     parser.add_argument('--data-cache-gb', type=float, default=64, help='--data-cache device: most GiB of decoded images to keep per GPU')
+    parser.add_argument('--quality-metrics', type=str, default='false', choices=['true', 'false'],
+                        help="image quality of the generator against the ground truth (SSIM as tf.image.ssim, PSNR, MAE), computed on "
+                             "the GPU: --train writes logs/val_quality.json (per epoch) and logs/test_quality.json, --predict "
+                             "writes logs/prediction_metrics.json")
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')
@@ -262,7 +311,9 @@ def main(opt):
             if info.is_main:
                 dataset, _, _ = p2p.image_pipeline(predict=True)
                 checkpoint.restore(latest_checkpoint(opt.weights))
-                p2p.predict(dataset, run.root)
+                metrics = p2p.predict(dataset, run.root)
+                if metrics is not None:
+                    run.write_json('prediction_metrics.json', summary(metrics))
         else:
             train, validation, test = p2p.image_pipeline(predict=False)
             manager = (CheckpointManager(checkpoint, os.path.join(run.root, 'training_checkpoints'), max_to_keep=1)
@@ -270,6 +321,9 @@ def main(opt):
             train_metrics, val_metrics = p2p.fit(train, validation, test, run.root, checkpoint_manager=manager)
             ddp.assert_replicas_in_sync([p2p.generator.net.params, p2p.discriminator.net.params], info)
             if info.is_main:
+                if opt.quality_metrics == 'true':
+                    run.write_json('val_quality.json', {k: [v if np.isfinite(v) else None for v in vs] for k, vs in p2p.val_quality.items()})
+                    run.write_json('test_quality.json', summary(p2p.evaluate(test)))
                 final = run.dir('final_test_imgs', fresh=True)
                 for k, (inp, tar) in enumerate(test.unbatch()):
                     p2p.generate_images(p2p.generator, inp[None], tar[None], os.path.join(final, f"img{k}.png"))

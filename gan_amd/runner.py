@@ -92,10 +92,12 @@ def plot_loss_curves(train: dict, val: dict, model_name: str, out_dir: str) -> N
         plt.close(fig)
 
 
-def run_epochs(epochs: int, keys, train_batches, val_batches, step, on_checkpoint, on_sample, headline, epoch_mean=None, after_pass=None):
+def run_epochs(epochs: int, keys, train_batches, val_batches, step, on_checkpoint, on_sample, headline, epoch_mean=None, after_pass=None,
+               after_epoch=None):
     """Epoch driver.  train_batches()/val_batches() yield the positional arguments of `step(*args, training)`, which
     returns the per-step loss tensors (device); `headline` = (train key, val key) printed per epoch.
     epoch_mean(acc, n) -> mean loss vector of a pass (data-parallel runs: over all ranks' steps, gan_amd.ddp.mean_over_ranks).
+    after_epoch(epoch) -> None or one more line for the epoch print; runs after the validation pass (image-quality metrics).
     Returns (train_cost_functions, val_cost_functions): {key: [epoch mean, ...]}."""
     hist = {k: [] for k in keys}, {k: [] for k in keys}
     t0 = time.time()
@@ -116,6 +118,7 @@ def run_epochs(epochs: int, keys, train_batches, val_batches, step, on_checkpoin
         for h, means in zip(hist, sums):
             for k, v in zip(keys, means):
                 h[k].append(v)
+        extra = after_epoch(epoch) if after_epoch is not None else None
         last = epoch == epochs
         if epoch % 5 == 0 or last:
             on_checkpoint()
@@ -123,5 +126,6 @@ def run_epochs(epochs: int, keys, train_batches, val_batches, step, on_checkpoin
                 on_sample(epoch)
         print(f'\nCumulative training duration at end of epoch {epoch}: {(time.time() - t0) / 60:.2f} min')
         print(f"Train {headline[0]}: {hist[0][headline[0]][-1]:.2f}, {headline[1]}: {hist[0][headline[1]][-1]:.2f}; "
-              f"val {headline[0]}: {hist[1][headline[0]][-1]:.2f}, {headline[1]}: {hist[1][headline[1]][-1]:.2f}\n", flush=True)
+              f"val {headline[0]}: {hist[1][headline[0]][-1]:.2f}, {headline[1]}: {hist[1][headline[1]][-1]:.2f}"
+              + (f"\n{extra}" if extra else "") + "\n", flush=True)
     return hist

@@ -471,6 +471,35 @@ typedef struct GanAugmentDesc {
  * them are found before anything is launched. */
 int gan_augment_u8(const GanAugmentDesc* d, gan_stream_t stream);
 
+/* ---- image-quality metrics ---------------------------------------------------------------------- */
+/* Per image of a batch of pairs, on the display range u = 0.5 * x + 0.5 (the mapping generate_images plots, pix2pix.py:236; inputs in
+ * [-1, 1], max_val = 1): out[i] = {ssim, psnr, mae, mse}.
+ *   ssim = tf.image.ssim(u_a, u_b, max_val=1, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03): Gaussian window applied
+ *          separably with VALID padding (map (h-10) x (w-10)); per channel lum * cs with
+ *          lum = (2 mx my + c1) / (mx^2 + my^2 + c1), cs = (2 F(ab) - 2 mx my + c2) / (F(a^2 + b^2) - mx^2 - my^2 + c2),
+ *          c1 = 1e-4, c2 = 9e-4; mean over the map, then over the channels.  Exactly 1 for a == b.
+ *   mae = mean |u_a - u_b|, mse = mean (u_a - u_b)^2 over h * w * c, psnr = -10 log10(mse) (tf.image.psnr; +inf for mse = 0).
+ * The reference itself only ever calls tf.image.ssim on (input, target) (pix2pix.py:182-184); this is the measurement between the
+ * generator's output and the target.  a and b: same n, h, w, c with c = 1 or 3, 11 <= h, w <= 4096, each of its own dtype and
+ * pitch (a channel-slice view of a wider buffer is fine: only the c real channels are read).  Two launches: fp32 partial sums per
+ * (image, 32 x 32 tile of the map) into the workspace, then one fixed-order sum per image - no atomics, bit-identical from call
+ * to call, an image's row independent of the rest of the batch. */
+typedef struct GanQualityDesc {
+  uint32_t struct_size;
+  int32_t dtype_a;             /* GAN_F32 | GAN_BF16 | GAN_F16: storage of a */
+  int32_t dtype_b;             /* the same for b */
+  GanTensor a;
+  GanTensor b;
+  float* out;                  /* device: [n][4] = {ssim, psnr, mae, mse} */
+  void* workspace;             /* device: >= gan_image_quality_workspace_bytes(n, h, w, c), 4-byte aligned */
+  size_t workspace_bytes;
+} GanQualityDesc;
+/* 0 for a shape gan_image_quality refuses */
+size_t gan_image_quality_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c);
+/* GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype, c not 1 or 3, n / h / w / c of a and b differ, n < 1, pitch < c.
+ * GAN_E_SHAPE: h or w below 11 or above 4096.  GAN_E_WORKSPACE: workspace too small.  All found before anything is launched. */
+int gan_image_quality(const GanQualityDesc* d, gan_stream_t stream);
+
 /* Host utility (no GPU): CRC-32C of TensorFlow's TensorBundle checkpoint files (tf.train.Checkpoint /
  * CheckpointManager, pix2pix.py:400-403,419-420; cycle_gan.py:437-444,460-461).  crc = 0 to start; chainable. */
 uint32_t gan_crc32c(uint32_t crc, const void* data, size_t n);
