@@ -857,10 +857,14 @@ class GenCall:
         self._bwd_cache = {}
         self.adam_fused = {}
         self.wire_direct = {}
-        # kernels whose wgrad launch runs on a SECOND wgrad lane (own slab workspace) in the staged schedule: set by the step object
-        # before the first backward op list is built (Pix2PixStep.wgrad_alt)
+        # Options of the step object (Pix2PixStep._settle_gen_options), settled before the first backward op list is built: the kernels
+        # whose wgrad launch runs on a SECOND wgrad lane (own slab workspace) in the staged schedule; the head's bias gradient as a
+        # side-stream op
         self.alt_wgrad = frozenset()
-        self.wgrad_stream2 = None
+        self.bias_grad_on_side = False
+        # backward(defer_wgrads='staged'): the wgrad lane, the second one (or None) and the stage cuts - set by the caller before each pass
+        self.wgrad_stream = self.wgrad_stream2 = None
+        self.wgrad_cuts = ()
 
     def _build_bwd(self, use_dgen2, need_dx, accumulate, wgrads='own', adam=None, wire=None):
         """wgrads: 'own' - this call's kernel gradients (accumulate as the other gradients do); 'none' - a guest call whose host
@@ -902,7 +906,7 @@ class GenCall:
         ops.append(bd.act_bwd(self.out.view(), self.dgen.view(), self.dgen2.view() if use_dgen2 else None,
                               self.dpre.view(), 'tanh'))
         wgrad(W(self.dpre).view(), W(self.cat[6]).view(), 'last.kernel', C_, 128, 2)
-        ops.append(bd.bias_grad(self.dpre.view(), P.ptr('last.bias', 'grad'), accumulate, side=bool(getattr(self, 'bias_grad_on_side', False))))
+        ops.append(bd.bias_grad(self.dpre.view(), P.ptr('last.bias', 'grad'), accumulate, side=self.bias_grad_on_side))
 
         def up_spec(j):         # backward of up j (ReLU [+ dropout] after the norm) on the leading G_UP[j] channels of dcat[j]
             mean, rstd = self.stats[f'up{j}']
@@ -1009,11 +1013,10 @@ class GenCall:
         dst = self.xin.view(0, self.C)
         L.check(self.ctx.lib.gan_copy_view(self.ctx.dt, C.byref(src_view), C.byref(dst), self.ctx.stream()), "copy_view")
 
-    def forward(self, inner_hook=None, masks_done=False):
+    def forward(self, inner_hook=None):
         """inner_hook: called when the op list reaches the inner layers (down3): a place to start independent work on
-        another lane that then runs beside the launch-latency-bound part of the generator.  masks_done: the caller has already
-        enqueued self.mask_ops elsewhere (a side lane) and orders them before the decoder itself."""
-        if self.auto_masks and not masks_done:
+        another lane that then runs beside the launch-latency-bound part of the generator."""
+        if self.auto_masks:
             self.ctx.run(self.mask_ops)
         if inner_hook is None:
             self.ctx.run(self.fwd_ops)
@@ -1049,7 +1052,7 @@ class GenCall:
             # layers before cut k start when the main dgrad/norm chain has passed cut k - per-op dependencies thrash
             # (two LDS-bound GEMMs on the same CUs), one stage at the very end leaves the tail serial
             main = self.ctx.lane_stream(0)
-            for k, (main_ops, w_ops) in enumerate(self.bwd_stages(self.wgrad_cuts, use_dgen2, need_dx, accumulate, wgrads, adam)):
+            for main_ops, w_ops in self.bwd_stages(self.wgrad_cuts, use_dgen2, need_dx, accumulate, wgrads, adam):
                 self.ctx.run(main_ops)
                 self.wgrad_stream.wait_stream(main)
                 two = self.wgrad_stream2 is not None
@@ -1058,8 +1061,6 @@ class GenCall:
                 if w2:           # second wgrad lane (forked from the origin stream, like every side lane)
                     self.wgrad_stream2.wait_stream(main)
                     self.ctx.run_on(w2, self.wgrad_stream2)
-                if getattr(self, 'stage_hook', None) is not None:
-                    self.stage_hook(k)         # e.g. the optimiser step of the layers whose gradients are now complete
         else:
             mkey = ('all', key)
             if mkey not in self._bwd_cache:

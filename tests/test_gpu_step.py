@@ -897,3 +897,46 @@ def test_bench_plain_run_times_its_steps_and_dumps_identical_outputs(tmp_path):
     assert dumps[0].keys() == dumps[1].keys()
     for f in dumps[0]:
         assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
+@pytest.mark.parametrize('model', ['pix2pix', 'cyclegan'])
+def test_the_schedule_of_a_call_depends_on_its_arguments_not_on_the_objects_past(model):
+    """bf16, 256^2 (Pix2Pix batch 2, CycleGAN batch 1).  On ONE step object: an eager training step, capture(training=True) with
+    two replays, a bare _forward_backward(x, y, False), a second eager training step.  Both eager steps enqueue exactly the same
+    kernels in the same order (diag.launch_log), the same as the first eager step of a freshly built object, and afterwards
+    nothing is left in the record of optimiser work done inside the backward pass (_in_step): no schedule decision survives
+    the call it was taken for."""
+    from gan_amd import _lib as L
+    from gan_amd.nets import Ctx
+    from gan_amd.steps import CycleGANStep, Pix2PixStep
+    B = 2 if model == 'pix2pix' else 1
+    a, b = O.synthetic_pair(B, 256, 1, seed=43)
+
+    def build():
+        ctx = Ctx('cuda:0', 'bf16')
+        st = Pix2PixStep(ctx, B, 256, 1, seed=7) if model == 'pix2pix' else CycleGANStep(ctx, B, 256, 1, seed=7)
+        return st, [torch.from_numpy(a).to(ctx.device), torch.from_numpy(b).to(ctx.device)]
+
+    def logged_eager_step(st, x):
+        L.set_option('diag.launch_log', 1)
+        try:
+            st.train_step(*x, True)
+            return L.launch_log()
+        finally:
+            L.set_option('diag.launch_log', 0)
+
+    st, x = build()
+    first = logged_eager_step(st, x)
+    replay = st.capture(training=True)
+    for _ in range(2):
+        replay(*x)
+    st._forward_backward(*x, False)
+    second = logged_eager_step(st, x)
+    torch.cuda.synchronize()
+    fresh = logged_eager_step(*build())
+    torch.cuda.synchronize()
+    print(f"[{model}] launches per eager step: {len(first)} | {len(second)} | fresh object {len(fresh)}")
+    assert len(first) > 100
+    assert first == second, [(i, p, q) for i, (p, q) in enumerate(zip(first, second)) if p != q][:3]
+    assert first == fresh, [(i, p, q) for i, (p, q) in enumerate(zip(first, fresh)) if p != q][:3]
+    assert not st._in_step and st._in_step.done == () and st._in_step.wfused == {}
