@@ -116,6 +116,19 @@ class GanQualityDesc(_Desc):
                 ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class GanTileGatherDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("src", C.c_void_p), ("src_bytes", C.c_int64),
+                ("src_pitch", C.c_int32), ("col0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32),
+                ("tile", C.c_int32), ("overlap", C.c_int32), ("t0", C.c_int32), ("n", C.c_int32), ("lut", C.c_void_p),
+                ("dst", GanTensor)]
+
+
+class GanTileBlendDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("tiles", GanTensor), ("image", C.c_void_p), ("h", C.c_int32),
+                ("w", C.c_int32), ("c", C.c_int32), ("tile", C.c_int32), ("overlap", C.c_int32), ("t0", C.c_int32), ("n", C.c_int32),
+                ("accumulate", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/gan_amd.h declares
 SYMBOLS = {
     "gan_conv2d_fwd": (C.c_int, [C.POINTER(GanConvDesc), C.c_void_p]),
@@ -176,6 +189,9 @@ SYMBOLS = {
     "gan_augment_u8": (C.c_int, [C.POINTER(GanAugmentDesc), C.c_void_p]),
     "gan_image_quality_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gan_image_quality": (C.c_int, [C.POINTER(GanQualityDesc), C.c_void_p]),
+    "gan_tile_grid": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gan_tile_gather_u8": (C.c_int, [C.POINTER(GanTileGatherDesc), C.c_void_p]),
+    "gan_tile_blend": (C.c_int, [C.POINTER(GanTileBlendDesc), C.c_void_p]),
     "gan_crc32c": (C.c_uint32, [C.c_uint32, C.c_void_p, C.c_size_t]),
     "gan_version": (C.c_char_p, []),
     "gan_set_option": (C.c_int, [C.c_char_p, C.c_int32]),

@@ -19,6 +19,7 @@ import torch
 
 from . import _lib as L
 from . import data as D
+from . import tiling
 from .checkpoint import DISC_LAYERS, GEN_LAYERS, tf_variable_key
 from .nets import Ctx, DiscriminatorNet, GeneratorNet, workspace_mb_for
 
@@ -90,16 +91,23 @@ class GeneratorModel(_Model):
     def infer_call(self, x, fold=True):
         """infer() up to the forward: -> the eval call, whose typed output view (out_view()) holds the prediction until the next
         call of this batch size (gan_amd.quality reads it there, without the unpack)."""
-        ctx = self.net.ctx
-        x = _to_dev(x, ctx)
-        B, S = x.shape[0], x.shape[1]
-        key = (B, S)
-        if key not in self._eval_calls:
-            self._eval_calls[key] = self.net.new_eval_call(B, S)
-        call = self._eval_calls[key]
+        x = _to_dev(x, self.net.ctx)
+        call = self.eval_call(x.shape[0], x.shape[1])
         call.set_input(x)
         call.infer(fold=fold)
         return call
+
+    def eval_call(self, batch, size):
+        """The (cached) inference call of this batch and image size."""
+        key = (batch, size)
+        if key not in self._eval_calls:
+            self._eval_calls[key] = self.net.new_eval_call(batch, size)
+        return self._eval_calls[key]
+
+    def infer_tiled(self, src_u8, *, tile, overlap, col0=0, width=None, batch=None, fold=True):
+        """Inference mode over a whole uint8 device image [H, W, C] of any size >= tile: overlapping tile x tile pieces through
+        the eval call as a batch, blended back on the device -> fp32 device tensor [H, width, C] (gan_amd/tiling.py)."""
+        return tiling.infer_tiled(self, src_u8, tile=tile, overlap=overlap, col0=col0, width=width, batch=batch, fold=fold)
 
 
 class DiscriminatorModel(_Model):

@@ -12,6 +12,7 @@ import torch
 
 from . import data as D
 from . import ddp
+from . import tiling
 from .base_gan import GAN
 from .checkpoint import Checkpoint, CheckpointManager, latest_checkpoint
 from .quality import QualityMeter, image_quality, summary
@@ -213,11 +214,15 @@ class Pix2Pix(GAN):
         """config['predict_training'] 'true' (default): the reference's batch-1 `generator(x, training=True)` per image.  'false':
         inference mode (moving statistics, no dropout), folded once - the weights stay fixed while predicting - and run in batches
         of config['batch_size'] images; the same files in the same order.
+        config['predict_resolution'] 'native' (inference mode only): every half at its source size, tiled (_predict_native).
         config['quality_metrics'] 'true': -> the image-quality metrics of the very predictions that are written as images, per
         image in file order (Pix2Pix.evaluate's layout); otherwise None."""
         plot_path = os.path.join(output_path, 'prediction_images')
         os.makedirs(plot_path, exist_ok=False)
         meter = QualityMeter() if str(self.config.get('quality_metrics', 'false')) == 'true' else None
+        if str(self.config.get('predict_resolution', 'resized')) == 'native':
+            self._predict_native(predict_ds.files, plot_path, meter)
+            return meter.drain() if meter is not None else None
         if str(self.config.get('predict_training', 'true')) == 'true':
             for k, (inp, tar) in enumerate(predict_ds.unbatch()):
                 self.generate_images(self.generator, inp[None], tar[None], os.path.join(plot_path, f"img{k}.png"), quality=meter)
@@ -234,6 +239,35 @@ class Pix2Pix(GAN):
                             gray=self.config['channels'] == '1')
                 k += 1
         return meter.drain() if meter is not None else None
+
+    def _predict_native(self, files, plot_path, meter):
+        """Prediction at the source resolution: each file is decoded once and uploaded once as uint8, input
+        and target are its two halves by column offset, the input goes through the generator as overlapping img_size tiles
+        (GeneratorModel.infer_tiled) and the three panels are written at the source size.  The metrics compare the full-resolution
+        prediction with the full-resolution normalised target."""
+        S, c = int(self.config['img_size']), int(self.config['channels'])
+        V = self.config.get('tile_overlap')
+        V = S // 4 if V is None else int(V)
+        lut = tiling.normalize_lut(self.ctx)
+        self.generator.fold()           # once: the weights stand still while predicting
+        for k, f in enumerate(files):
+            img = D.decode(f, c)
+            H, W = img.shape[:2]
+            half = W // 2
+            if W % 2:
+                raise ValueError(f"{f}: a pair of odd width {W} has halves of different sizes; --predict-resolution native "
+                                 "compares the halves pixel by pixel and does not resize")
+            if H < S or half < S:
+                raise ValueError(f"{f}: each half is {H} x {half}, smaller than --img-size {S}; --predict-resolution native does "
+                                 "not pad (use --predict-resolution resized)")
+            ci, ct = (0, half) if self.config['input_img_orient'] == 'left' else (half, 0)
+            src = torch.from_numpy(img.copy()).to(self.ctx.device)      # the one upload
+            pred = self.generator.infer_tiled(src, tile=S, overlap=V, col0=ci, width=half, fold=False)
+            if meter is not None:
+                meter.add(image_quality(self.ctx, pred[None], lut[src[:, ct:ct + half].long()][None]))
+            host = lambda c0: D.normalize(img[:, c0:c0 + half].astype(np.float32))
+            save_panels(os.path.join(plot_path, f"img{k}.png"), [('Input Image', host(ci)), ('Ground Truth', host(ct)),
+                                                                 ('Predicted Image', pred.cpu().numpy())], gray=self.config['channels'] == '1')
 
 
 def parse_opt(argv=None):
@@ -266,6 +300,11 @@ def parse_opt(argv=None):
     parser.add_argument('--predict-training', type=str, default='true', choices=['true', 'false'],
                         help="--predict only: 'true' = the reference's generator(x, training=True) at batch 1 (batch statistics, "
                              "dropout); 'false' = Keras inference mode (moving statistics, no dropout) in batches of --batch-size")
+    parser.add_argument('--predict-resolution', type=str, default='resized', choices=['resized', 'native'],
+                        help="--predict only: 'resized' = every half resized to --img-size first (the reference); 'native' = predict "
+                             "at the source size from overlapping --img-size tiles blended on the GPU (needs --predict-training false)")
+    parser.add_argument('--tile-overlap', type=int, default=None,
+                        help='--predict-resolution native: pixels neighbouring tiles share, 0 ..= img-size / 2 (default img-size / 4)')
     parser.add_argument('--data-cache', type=str, default='host', choices=['host', 'device'],
                         help="--train: 'host' decodes and augments every image on the CPU in every epoch; 'device' decodes each file once, "
                              "keeps the uint8 images in GPU memory and builds every batch there (identical batches)")
@@ -288,6 +327,13 @@ def parse_opt(argv=None):
         parser.error("--generator-loss ssim is not supported by gan_amd (the reference's SSIM term compares input with target and "
                      "carries no gradient, pix2pix.py:182-184); use the default --generator-loss l1")
     assert (args.img_size == 256) or (args.img_size == 512), "img-size currently only supported for 256 x 256 or 512 x 512 pixels!"
+    if args.tile_overlap is None:
+        args.tile_overlap = args.img_size // 4
+    if not 0 <= args.tile_overlap <= args.img_size // 2:
+        parser.error(f"--tile-overlap {args.tile_overlap} is outside [0, img-size / 2 = {args.img_size // 2}]")
+    if args.predict_resolution == 'native' and not (args.predict and args.predict_training == 'false'):
+        parser.error("--predict-resolution native requires --predict and --predict-training false: tiles are only meaningful in "
+                     "inference mode (batch statistics over the tiles of one image are not the reference's semantics)")
     assert (args.validation_size > 0.0 and args.validation_size <= 0.3), "validation size is a proportion and bounded between 0-0.3!"
     assert (args.test_img >= 1), "test-img is an integer and must be >=1!"
     return args

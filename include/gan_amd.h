@@ -500,6 +500,68 @@ size_t gan_image_quality_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_
  * GAN_E_SHAPE: h or w below 11 or above 4096.  GAN_E_WORKSPACE: workspace too small.  All found before anything is launched. */
 int gan_image_quality(const GanQualityDesc* d, gan_stream_t stream);
 
+/* ---- tiled inference: cut an image into overlapping network-sized tiles, blend the predictions back ------------------ */
+/* Prediction at the source resolution (no counterpart in the reference, which resizes every image to img_size x img_size first,
+ * pix2pix.py:43-52): an h x w image is cut into overlapping tile x tile pieces, the pieces go through one inference call as a
+ * batch, and the outputs are blended back with weights that fall off towards the tile edges.
+ * Geometry, per image axis of length L, with tile size S, overlap V and stride T = S - V:
+ *     count n = 1 if L == S, else ceil((L - S) / T) + 1;   origin of tile k = min(k * T, L - S)
+ * (the last tile is pulled back to end at the image edge: nothing is padded or extrapolated); the tiles of an image are
+ * numbered row-major, t = ky * nx + kx.  Valid: L >= S, 0 <= V <= S / 2, S a multiple of 8 in [16, 1024], h and w <= 4096 -
+ * then at most 3 tiles cover a pixel per axis, 9 in all.
+ * Blend weight, per axis: the integer hat of the offset i inside the tile (0 <= i < S), hat(i) = min(i + 1, S - i) >= 1.  For
+ * the image coordinate p, over the tiles k of the WHOLE grid that cover p, i_k = p - origin_k:
+ *     a_k(p) = float(hat(i_k)) / float(sum_j hat(i_j))          one fp32 division of exactly representable integers
+ * and for the pixel (py, px), channel ch:
+ *     out = sum over ky ascending, inside it over kx ascending, of (a_ky(py) * a_kx(px)) * tile_value
+ * Every product and every addition is rounded to fp32 on its own (nothing is contracted), the terms are added in that fixed
+ * order, and the sum starts from 0.0f (accumulate = 0) or from the stored value (accumulate = 1).  A pixel that one tile covers
+ * has weight exactly 1.0. */
+/* Host only: the tile counts of an h x w image.  GAN_E_ARG: ny or nx NULL; GAN_E_SHAPE: the geometry is not valid (above). */
+int gan_tile_grid(int32_t h, int32_t w, int32_t tile, int32_t overlap, int32_t* ny, int32_t* nx);
+
+/* Tiles [t0, t0 + n) of one uint8 image, straight into a typed network input:
+ *     dst[t - t0][r][x][ch] = dtype( lut[ src[(oy(t) + r) * src_pitch + (col0 + ox(t) + x) * c + ch] ] )
+ * with (oy, ox) the origin of tile t.  Only the c real channels of a destination pixel are written: the pad channels of a wider
+ * pitch keep what they hold, exactly as gan_pack leaves them.  Every source read is clamped to [0, src_bytes). */
+typedef struct GanTileGatherDesc {
+  uint32_t struct_size;
+  int32_t dtype;               /* storage of dst: GAN_F32 | GAN_BF16 | GAN_F16 (round to nearest, as every conversion here) */
+  const uint8_t* src;          /* device: first byte of the image's first row; c interleaved channels */
+  int64_t src_bytes;           /* bytes readable from src */
+  int32_t src_pitch;           /* bytes between consecutive source rows */
+  int32_t col0;                /* first source column (pixels) of the part used: 0, or width / 2 for the right half of a pair */
+  int32_t h, w;                /* size of the part used */
+  int32_t c;                   /* 1 or 3 */
+  int32_t tile, overlap;
+  int32_t t0, n;               /* tiles of this launch */
+  const float* lut;            /* device: 256 fp32 values, the normalised value of every byte (GanAugmentDesc.lut) */
+  GanTensor dst;               /* n x tile x tile, c channels, own pitch; ptr aligned to its element size */
+} GanTileGatherDesc;
+/* GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype, c not 1 or 3, dst not n x tile x tile x c, pitch < c, t0 / n outside the
+ * grid, dst.ptr not element-aligned or lut not 4-byte aligned, col0 / src_pitch / the last row outside src_bytes.
+ * GAN_E_SHAPE: as gan_tile_grid.  All found before anything is launched; enqueue-only. */
+int gan_tile_gather_u8(const GanTileGatherDesc* d, gan_stream_t stream);
+
+/* Tiles [t0, t0 + n) of a typed network output, added into the dense fp32 image [h][w][c] with the weights above.  One thread
+ * owns an output pixel: it finds the tiles of this launch that cover it, adds them in ascending tile order and writes once -
+ * no atomics, bit-identical from call to call.  A pixel that no tile of the launch covers keeps its value (accumulate = 1) or
+ * becomes 0 (accumulate = 0).  The tiles of an image split over several launches in ascending order (accumulate = 0, then 1)
+ * give the same bits as one launch. */
+typedef struct GanTileBlendDesc {
+  uint32_t struct_size;
+  int32_t dtype;               /* storage of tiles */
+  GanTensor tiles;             /* n x tile x tile, c channels, own pitch (the generator's output view) */
+  float* image;                /* device: dense fp32 [h][w][c], 4-byte aligned */
+  int32_t h, w, c;
+  int32_t tile, overlap;
+  int32_t t0, n;
+  int32_t accumulate;          /* 0: start from 0.0f and overwrite; 1: start from the stored value */
+} GanTileBlendDesc;
+/* GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype, c not 1 or 3, tiles not n x tile x tile x c, pitch < c, t0 / n outside
+ * the grid, accumulate not 0 or 1, tiles.ptr not element-aligned or image not 4-byte aligned.  GAN_E_SHAPE: as gan_tile_grid. */
+int gan_tile_blend(const GanTileBlendDesc* d, gan_stream_t stream);
+
 /* Host utility (no GPU): CRC-32C of TensorFlow's TensorBundle checkpoint files (tf.train.Checkpoint /
  * CheckpointManager, pix2pix.py:400-403,419-420; cycle_gan.py:437-444,460-461).  crc = 0 to start; chainable. */
 uint32_t gan_crc32c(uint32_t crc, const void* data, size_t n);
