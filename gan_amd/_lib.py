@@ -116,6 +116,13 @@ class GanQualityDesc(_Desc):
                 ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class GanDssimDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("dtype_a", C.c_int32), ("dtype_b", C.c_int32), ("a", GanTensor), ("b", GanTensor),
+                ("loss_scale", C.c_float), ("loss_accumulate", C.c_int32), ("loss_out", C.c_void_p), ("grad_scale", C.c_float),
+                ("dtype_da", C.c_int32), ("da", GanTensor), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("scale_state", C.c_void_p)]
+
+
 class GanTileGatherDesc(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("src", C.c_void_p), ("src_bytes", C.c_int64),
                 ("src_pitch", C.c_int32), ("col0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32),
@@ -189,6 +196,8 @@ SYMBOLS = {
     "gan_augment_u8": (C.c_int, [C.POINTER(GanAugmentDesc), C.c_void_p]),
     "gan_image_quality_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gan_image_quality": (C.c_int, [C.POINTER(GanQualityDesc), C.c_void_p]),
+    "gan_dssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gan_dssim": (C.c_int, [C.POINTER(GanDssimDesc), C.c_void_p]),
     "gan_tile_grid": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gan_tile_gather_u8": (C.c_int, [C.POINTER(GanTileGatherDesc), C.c_void_p]),
     "gan_tile_blend": (C.c_int, [C.POINTER(GanTileBlendDesc), C.c_void_p]),

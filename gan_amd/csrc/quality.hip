@@ -16,15 +16,14 @@
 // the definition's second moments with operands of a quarter of the magnitude (|x'| <= 0.5 against u <= 1): less cancellation where
 // it hurts, on bright flat images, at no cost.  Only the luminance term needs the means themselves: mx = F(x') + 0.5.
 #include "common.h"
+#include "ssim_window.h"
 
 namespace {
 
 constexpr int QT = 32;            // tile edge of the SSIM map
-constexpr int QK = 11;            // filter taps
+constexpr int QK = SSIM_K;        // filter taps (ssim_window.h: the window, c1, c2 and the rounding discipline, shared with dssim.hip)
 constexpr int QS = QT + QK - 1;   // staged edge: 42
 constexpr int QTHREADS = 256;
-constexpr float QC1 = 1e-4f;      // (0.01 * max_val)^2
-constexpr float QC2 = 9e-4f;      // (0.03 * max_val)^2
 
 struct QualityArgs {
   const void* a;
@@ -35,12 +34,6 @@ struct QualityArgs {
   float g[QK];                    // Gaussian window, normalised in double on the host
   float* partial;                 // [n][tiles_y * tiles_x][4]: {sum lum*cs, sum |x'-y'|, sum (x'-y')^2, 0}
 };
-
-// products whose roundings must not be fused into the additions that follow: with a == b the sums below are then exact doubles of
-// each other and SSIM comes out as exactly 1
-__device__ __forceinline__ float q_mul(float x, float y) { return __fmul_rn(x, y); }
-__device__ __forceinline__ float q_add(float x, float y) { return __fadd_rn(x, y); }
-__device__ __forceinline__ float q_sub(float x, float y) { return __fsub_rn(x, y); }
 
 template <typename TA, typename TB>
 __global__ __launch_bounds__(QTHREADS) void quality_tile_kernel(const QualityArgs q) {
@@ -109,12 +102,8 @@ __global__ __launch_bounds__(QTHREADS) void quality_tile_kernel(const QualityArg
           eab = fmaf(wk, hm[2][r + k][x], eab);
           esq = fmaf(wk, hm[3][r + k][x], esq);
         }
-        const float mx = q_add(ma, 0.5f), my = q_add(mb, 0.5f);
-        const float lum_n = q_add(q_mul(2.f, q_mul(mx, my)), QC1);
-        const float lum_d = q_add(q_add(q_mul(mx, mx), q_mul(my, my)), QC1);
-        const float cs_n = q_add(q_sub(q_mul(2.f, eab), q_mul(2.f, q_mul(ma, mb))), QC2);
-        const float cs_d = q_add(q_sub(esq, q_add(q_mul(ma, ma), q_mul(mb, mb))), QC2);
-        s_ssim += q_mul(lum_n / lum_d, cs_n / cs_d);
+        const SsimTerms t = ssim_terms(ma, mb, eab, esq);
+        s_ssim += q_mul(t.lum, t.cs);
       }
     }
     // fixed-order workgroup sum: butterfly inside each wave, then the four wave sums in order
@@ -195,9 +184,7 @@ extern "C" int gan_image_quality(const GanQualityDesc* d, gan_stream_t stream) {
   q.a = a.ptr; q.b = b.ptr; q.pitch_a = a.pitch; q.pitch_b = b.pitch;
   q.n = a.n; q.h = a.h; q.w = a.w; q.c = a.c;
   q.tiles_x = q_tiles(a.w); q.tiles_y = q_tiles(a.h);
-  double g[QK], sum = 0.0;
-  for (int k = 0; k < QK; ++k) sum += g[k] = exp(-(double)((k - 5) * (k - 5)) / (2.0 * 1.5 * 1.5));
-  for (int k = 0; k < QK; ++k) q.g[k] = (float)(g[k] / sum);
+  ssim_window(q.g);
   q.partial = (float*)d->workspace;
   hipStream_t st = (hipStream_t)stream;
   const int tiles = q.tiles_x * q.tiles_y;

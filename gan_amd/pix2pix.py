@@ -37,6 +37,22 @@ def _restore_step_state(saved):
         t.copy_(v)
 
 
+def _dssim_eager(a, b):
+    """1 - mean SSIM(a, b) of two NHWC batches in [-1, 1]: the eager torch restatement of gan_dssim (DESIGN.md section 14;
+    tf.image.ssim on the display range 0.5 * x + 0.5 with max_val 1), differentiable through autograd."""
+    ua, ub = (0.5 * t.float().permute(0, 3, 1, 2) + 0.5 for t in (a, b))
+    c = ua.shape[1]
+    k = torch.arange(11, dtype=torch.float64, device=ua.device) - 5
+    g = torch.exp(-k * k / (2 * 1.5 ** 2))
+    g = (g / g.sum()).float()
+    win = (g[:, None] * g[None, :]).expand(c, 1, 11, 11).contiguous()
+    F = lambda t: torch.nn.functional.conv2d(t, win, groups=c)
+    mx, my = F(ua), F(ub)
+    lum = (2 * mx * my + 1e-4) / (mx * mx + my * my + 1e-4)
+    cs = (2 * (F(ua * ub) - mx * my) + 9e-4) / (F(ua * ua + ub * ub) - mx * mx - my * my + 9e-4)
+    return 1.0 - (lum * cs).mean()
+
+
 class Pix2Pix(GAN):
     def __init__(self, config):
         super().__init__(config)
@@ -109,8 +125,10 @@ class Pix2Pix(GAN):
     # ---- losses / step (pix2pix.py:167-218) ------------------------------------------------------
     def generator_loss(self, disc_generated_output, gen_output, target, input_image):
         gan_loss = self.loss_obj(1.0, disc_generated_output)
-        assert self.config['generator_loss'] == 'l1', "only the default l1 secondary loss is on the accelerated path"
-        gan_loss2 = (torch.as_tensor(target, device=self.ctx.device).float() - gen_output).abs().mean()
+        kind = self.config['generator_loss']
+        assert kind in ('l1', 'dssim'), "the secondary generator loss is 'l1' or 'dssim' ('ssim' is refused by parse_opt)"
+        target = torch.as_tensor(target, device=self.ctx.device).float()
+        gan_loss2 = _dssim_eager(gen_output, target) if kind == 'dssim' else (target - gen_output).abs().mean()
         return gan_loss + (self.config['lambda'] * gan_loss2), gan_loss, gan_loss2
 
     def _step_for(self, batch, training):
@@ -118,7 +136,8 @@ class Pix2Pix(GAN):
         if key not in self._steps:
             st = Pix2PixStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
                              lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
-                             seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net))
+                             seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net),
+                             generator_loss=self.config.get('generator_loss', 'l1'))
             st.sync = self.sync
             saved = self._snapshot()       # capture() runs warm-up passes (they also move BatchNorm's moving statistics): undo them
             extra = _step_state(self.ctx, st)
@@ -281,7 +300,9 @@ def parse_opt(argv=None):
     parser.add_argument('--buffer-size', type=int, default=99999, help='buffer size')
     parser.add_argument('--channels', type=str, default='1', choices=['1', '3'], help='number of color channels to read in and output')
     parser.add_argument('--logging', type=str, default='true', choices=['true', 'false'], help='turn on/off script logging, e.g. for CLI debugging')
-    parser.add_argument('--generator-loss', type=str, default='l1', choices=['l1', 'ssim'], help='combined generator loss function')
+    parser.add_argument('--generator-loss', type=str, default='l1', choices=['l1', 'ssim', 'dssim'],
+                        help="secondary generator loss: 'l1' = mean |target - generated|; 'dssim' = 1 - mean SSIM(generated, target), computed "
+                             "with its gradient on the GPU; 'ssim' (the reference's input-against-target term) is refused")
     parser.add_argument('--input-img-orient', type=str, default='left', choices=['left', 'right'], help='whether input image is on left (i.e. target right) or vice-versa')
     parser.add_argument('--seed', type=int, default=123, help='seed value for random number generator')
     group = parser.add_mutually_exclusive_group(required=True)
@@ -289,7 +310,7 @@ def parse_opt(argv=None):
     group.add_argument('--predict', action='store_true', help='use pretrained weights to make predictions on data')
     parser.add_argument('--save-weights', type=str, default='true', choices=['true', 'false'], help='save model checkpoints and weights')
     parser.add_argument('--epochs', type=int, default=5, help='number of epochs to train', required='--train' in argv)
-    parser.add_argument('--lambda', type=int, default=100, help='lambda value for secondary generator loss (L1)')
+    parser.add_argument('--lambda', type=int, default=100, help='lambda value for secondary generator loss (L1 / dSSIM)')
     parser.add_argument('--validation-size', type=float, default=0.1, help='validation set size as share of number of training images')
     parser.add_argument('--test-img', type=int, default=5, help='number of test images to sample')
     parser.add_argument('--learning-rate', type=float, default=2e-4, help='learning rate for Adam optimizer for generator and discriminator')
@@ -325,7 +346,8 @@ def parse_opt(argv=None):
         # a (batch,) vector.  That degenerate term is not built here, and training silently with L1
         # under an 'ssim' label would not be a drop-in: refuse.
         parser.error("--generator-loss ssim is not supported by gan_amd (the reference's SSIM term compares input with target and "
-                     "carries no gradient, pix2pix.py:182-184); use the default --generator-loss l1")
+                     "carries no gradient, pix2pix.py:182-184); use the default --generator-loss l1, or --generator-loss dssim "
+                     "for 1 - SSIM(generated, target)")
     assert (args.img_size == 256) or (args.img_size == 512), "img-size currently only supported for 256 x 256 or 512 x 512 pixels!"
     if args.tile_overlap is None:
         args.tile_overlap = args.img_size // 4

@@ -275,8 +275,16 @@ class Pix2PixStep(_StepBase):
     ddp_wire_direct = True       # bf16 all-reduce exchange: wgrad launches write their gradients straight into the wire buffer
 
     def __init__(self, ctx: Ctx, batch, size, channels=1, lam=100.0, lr=2e-4, beta_1=0.5, beta_2=0.999,
-                 seed=123, dropout=True, nets=None, mask_stream=0):
+                 seed=123, dropout=True, nets=None, mask_stream=0, generator_loss='l1'):
+        if generator_loss not in ('l1', 'dssim'):
+            raise ValueError(f"generator_loss {generator_loss!r}: 'l1' or 'dssim'")
         super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=8)
+        self.generator_loss = generator_loss       # the secondary term (losses[2]): mean |target - gen|, or 1 - mean SSIM
+        if generator_loss == 'dssim':
+            need = ctx.lib.gan_dssim_workspace_bytes(batch, size, size, channels)
+            if not need:
+                raise ValueError(f"generator_loss 'dssim': unsupported shape {(batch, size, size, channels)}")
+            self.dssim_ws = torch.zeros(need // 4, dtype=torch.float32, device=ctx.device)
         if nets is not None:          # share weights with an existing step / model objects
             self.G, self.D = nets
         else:
@@ -288,6 +296,13 @@ class Pix2PixStep(_StepBase):
 
     def nets(self):
         return (self.G, self.D)
+
+    def _dssim(self, a, b, loss_idx, loss_scale, acc, grad_scale, da, stream=None):
+        """gan_dssim with _l1's contract: losses[loss_idx] (+)= loss_scale * (1 - mean SSIM(a, b)), da = grad_scale * d/da."""
+        ctx = self.ctx
+        d = L.GanDssimDesc(ctx.dt, ctx.dt, a, b, loss_scale, int(acc), self.losses.data_ptr() + 4 * loss_idx, grad_scale, ctx.dt,
+                           da if da is not None else L.GanTensor(), self.dssim_ws.data_ptr(), self.dssim_ws.numel() * 4, ctx.ls_ptr)
+        L.check(ctx.lib.gan_dssim(C.byref(d), stream.cuda_stream if stream is not None else ctx.stream()), "dssim")
 
     def _settle_gen_options(self):
         """The options of G's call that shape its backward op lists, taken from this object's switches when the first list is
@@ -341,12 +356,14 @@ class Pix2PixStep(_StepBase):
             ctx.join(main, side)                                      # D(real) done (its BatchNorm updates come first)
         else:
             g.forward()                                               # pix2pix.py:200
-        # generator loss (pix2pix.py:167-188): BCE(1, D(fake)) + lambda * mean|target - gen|; discriminator loss
+        # generator loss (pix2pix.py:167-188): BCE(1, D(fake)) + lambda * mean|target - gen| (or, generator_loss 'dssim', lambda *
+        # (1 - mean SSIM(gen, target)): same operands, stream and outputs); discriminator loss
         # (base_gan.py:233-245, factor 0.5 at pix2pix.py:206) - the L1 term (it only needs G's output: beside D's
         # forward when lanes are on), then all three BCE terms in one pass
         if side is not None:
             side.wait_stream(main)
-        self._l1(g.out_view(), d.xin.view(Cc, Cc, 0, B), 2, 1.0, False, self.lam, g.dgen.view(0, Cc), stream=side)
+        secondary = self._dssim if self.generator_loss == 'dssim' else self._l1
+        secondary(g.out_view(), d.xin.view(Cc, Cc, 0, B), 2, 1.0, False, self.lam, g.dgen.view(0, Cc), stream=side)
         self._copy(g.out_view(), d.xin.view(Cc, Cc, B, B))
         if dreal:
             ctx.run(d.forward_part_ops(1))                            # pix2pix.py:203

@@ -500,6 +500,42 @@ size_t gan_image_quality_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_
  * GAN_E_SHAPE: h or w below 11 or above 4096.  GAN_E_WORKSPACE: workspace too small.  All found before anything is launched. */
 int gan_image_quality(const GanQualityDesc* d, gan_stream_t stream);
 
+/* ---- structural dissimilarity as a training loss ------------------------------------------------- */
+/* loss = 1 - mean_i ssim_i with ssim_i exactly the `ssim` column of gan_image_quality (same window, constants, display range and
+ * centred arithmetic: loss is exactly 0 for a == b), and its gradient with respect to a (the prediction).  With mx = F(ua),
+ * my = F(ub), sxy = F(ua ub), sq = F(ua^2 + ub^2), A1 = 2 mx my + c1, B1 = mx^2 + my^2 + c1, A2 = 2 (sxy - mx my) + c2,
+ * B2 = sq - mx^2 - my^2 + c2, S = A1 A2 / (B1 B2) per map position and
+ *   P = dS/dmx = (2 my A2 - 2 my A1) / (B1 B2) - S (2 mx / B1 - 2 mx / B2),  Q = dS/dsxy = 2 A1 / (B1 B2),  R = dS/dsq = -S / B2,
+ *   dloss/da(p) = -0.5 / (n c |M|) * (G^T[P](p) + ub(p) G^T[Q](p) + 2 ua(p) G^T[R](p)),
+ * G^T[Z](p) = sum over the valid map positions q, 0 <= p - q <= 10 per axis, of g(py - qy) g(px - qx) Z(q)   (DESIGN.md section 14).
+ * No counterpart in the reference: its SSIM term compares the input with the target (pix2pix.py:182-184) and has no gradient.
+ * Two launches: one workgroup per (image, 32 x 32 tile of pixels) writes da once per pixel and one fp32 partial sum of S into the
+ * workspace, then one fixed-order sum (double) - no atomics, bit-identical from call to call, enqueue-only and capturable.  The
+ * value written for an image is its batch-1 gradient divided by n, rounded once: it does not depend on the rest of the batch. */
+typedef struct GanDssimDesc {
+  uint32_t struct_size;
+  int32_t dtype_a;             /* GAN_F32 | GAN_BF16 | GAN_F16: storage of a */
+  int32_t dtype_b;             /* the same for b */
+  GanTensor a;                 /* prediction: c = 1 or 3, own pitch; only the c real channels are read (pads may hold NaN) */
+  GanTensor b;                 /* target: same n, h, w, c; own dtype and pitch */
+  float loss_scale;
+  int32_t loss_accumulate;     /* 0 | 1 */
+  float* loss_out;             /* device: loss_out[0] (+)= loss_scale * loss, as gan_l1 */
+  float grad_scale;
+  int32_t dtype_da;            /* storage of da */
+  GanTensor da;                /* ptr NULL: loss only.  da = grad_scale * [scale_state[0]] * dloss/da rounded to dtype_da; same n, h,
+                                  w, c as a, own pitch; only the c real channels are written */
+  void* workspace;             /* device: >= gan_dssim_workspace_bytes(n, h, w, c), 4-byte aligned */
+  size_t workspace_bytes;
+  const float* scale_state;    /* fp16 loss scaling, as every loss entry point; NULL = none */
+} GanDssimDesc;
+/* 0 for a shape gan_dssim refuses */
+size_t gan_dssim_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c);
+/* GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype, c not 1 or 3, n / h / w / c of a, b (and da) differ, n < 1, pitch < c,
+ * loss_accumulate not 0 or 1.  GAN_E_SHAPE: h or w below 11 or above 4096.  GAN_E_WORKSPACE: workspace too small.  All found
+ * before anything is launched. */
+int gan_dssim(const GanDssimDesc* d, gan_stream_t stream);
+
 /* ---- tiled inference: cut an image into overlapping network-sized tiles, blend the predictions back ------------------ */
 /* Prediction at the source resolution (no counterpart in the reference, which resizes every image to img_size x img_size first,
  * pix2pix.py:43-52): an h x w image is cut into overlapping tile x tile pieces, the pieces go through one inference call as a
