@@ -65,6 +65,7 @@ __global__ __launch_bounds__(256) void patchgan_bce_kernel(const float* real, co
 }
 __global__ __launch_bounds__(64) void patchgan_finalize_kernel(const float* partial, int n, double inv_count, float lambda,
                                                                const float* l1, float* gen_total, float* gan_loss, float* disc_loss) {
+#pragma clang fp contract(off)         // gen_total is the plain fp32 gan + lambda * l1 (two roundings, as the reference's two ops), not an fma
   double s = 0;
   const int k = threadIdx.x;                          // lanes 0..2: one BCE term each, summed in block order
   if (k < 3)

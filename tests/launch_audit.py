@@ -47,26 +47,34 @@ QUERIES = {'gan_conv_plan_info', 'gan_conv_workspace_bytes', 'gan_wgrad_plan_inf
 
 # Recorded entry points that are not checked here, and why.
 ALLOWLIST = {
-    'gan_bce_logits': 'loss scalar + (sigmoid(x)-t)/n row: elementwise, checked against the oracle by test_gpu_ops::test_act_bwd_bias_grad_losses',
-    'gan_patchgan_losses': 'the three BCE terms in one pass: test_gpu_ops::test_patchgan_losses_equal_three_bce_calls + the step tests',
-    'gan_l1': 'mean |a-b| scalar + sign row: test_gpu_ops::test_act_bwd_bias_grad_losses',
-    'gan_sum3': 'three scalars added: the step tests compare the total generator loss with the oracle',
-    'gan_adam_begin': 'step counter + lr_t scalar: read back here as the input of every fused-Adam check (a wrong lr_t fails those)',
-    'gan_adam_tf': 'Adam of the norm / bias vectors (no planner choice): test_gpu_ops::test_adam_tf_and_weight_prep',
-    'gan_adam_prepare_multi': 'the flat multi-tensor Adam + NK refresh: test_gpu_ops::test_fused_adam_prepare_equals_adam_then_prepare; '
+    'gan_bce_logits': 'loss scalar + (sigmoid(x)-t)/n row: per element against fp64 (cap-crossing counts, planted +-0 / +-100 logits, scale '
+                      'state, loss_accumulate) by test_gpu_elementwise::test_bce_logits',
+    'gan_patchgan_losses': 'the three BCE terms in one pass: per element against fp64 by test_gpu_elementwise::test_patchgan_losses',
+    'gan_l1': 'mean |a-b| scalar + sign row (sign(0) = 0): per element against fp64 on pitched views by test_gpu_elementwise::test_l1',
+    'gan_sum3': 'three scalars added: bit-equal to the fp32 (a+b)+c by test_gpu_elementwise::test_sum3',
+    'gan_adam_begin': 'step counter + lr_t scalar: within one ulp of the extended-precision value at t = 1..100,000 and kept on a skipped '
+                      'step by test_gpu_elementwise::test_adam_begin; read back here as the input of every fused-Adam check',
+    'gan_adam_tf': 'Adam of the norm / bias vectors (no planner choice): m, v, p per element against fp64 (cap-crossing count, wire '
+                   'gradient, scale state, skipped step) by test_gpu_elementwise::test_adam_tf',
+    'gan_adam_prepare_multi': 'the flat multi-tensor Adam + NK refresh: bit-equal to gan_adam_tf + gan_weights_prepare (both checked by '
+                              'test_gpu_elementwise) in test_gpu_ops::test_fused_adam_prepare_equals_adam_then_prepare; '
                               'the NK copies it writes are the weights every later conv reads, decoded from the device here',
-    'gan_weights_prepare_multi': 'NK copies of the master: decoded from the device copy by every conv check here (not trusted)',
-    'gan_pack': 'fp32 -> storage cast of the inputs: test_gpu_ops::test_dropout_mask_and_pack',
-    'gan_pack_multi': 'test_gpu_ops::test_multi_launch_pack_and_dropout_equal_single_calls',
-    'gan_unpack': 'test_gpu_ops::test_dropout_mask_and_pack',
-    'gan_copy_view': 'a typed copy between views: its destination is an input read from the snapshot by the next checked call',
-    'gan_dropout_mask': 'counter-hash Bernoulli mask (no reference value exists): read here as an input of every dropout check',
-    'gan_dropout_mask_multi': 'as gan_dropout_mask: test_gpu_ops::test_multi_launch_pack_and_dropout_equal_single_calls',
-    'gan_grads_check': 'fp16 inf/nan flag of the loss scale: test_gpu_configs::test_loss_scale_state_machine, '
-                       'test_gpu_configs::test_pix2pix_f16_step_vs_oracle',
+    'gan_weights_prepare_multi': 'NK copies of the master: bit-equal to the cast master in both layouts, padding zeroed, by '
+                                 'test_gpu_elementwise::test_weights_prepare_multi; decoded from the device copy by every conv check here',
+    'gan_pack': 'fp32 -> storage cast of the inputs: bit-equal to round-to-nearest-even on ties, overflow, subnormals, inf, NaN by '
+                'test_gpu_elementwise::test_pack_unpack_copy_view',
+    'gan_pack_multi': 'as gan_pack, 1 and 4 pairs: test_gpu_elementwise::test_pack_unpack_copy_view',
+    'gan_unpack': 'exact widening: test_gpu_elementwise::test_pack_unpack_copy_view',
+    'gan_copy_view': 'a typed copy between views: bit-equal, nothing outside the view written, by '
+                     'test_gpu_elementwise::test_pack_unpack_copy_view',
+    'gan_dropout_mask': 'counter-hash Bernoulli mask: bit-equal to the integer SplitMix64 reference (elementwise_ref.mask_ref) by '
+                        'test_gpu_elementwise::test_dropout_masks; read here as an input of every dropout check',
+    'gan_dropout_mask_multi': 'as gan_dropout_mask, with the draw counter and the unaligned byte path: test_gpu_elementwise::test_dropout_masks',
+    'gan_grads_check': 'fp16 inf/nan flag of the loss scale: one inf / nan at the first, last (second trip) and a middle element by '
+                       'test_gpu_elementwise::test_grads_check; the state machine by test_gpu_configs::test_loss_scale_state_machine',
     'gan_loss_scale_update': 'fp16 loss-scale state machine: test_gpu_configs::test_loss_scale_state_machine',
-    'gan_grad_pack': 'data-parallel wire format (out of scope: multi-rank paths)',
-    'gan_grad_unpack': 'data-parallel wire format (out of scope: multi-rank paths)',
+    'gan_grad_pack': 'data-parallel wire format: bit-equal to the bf16 round-to-nearest-even cast by test_gpu_elementwise::test_grad_pack_unpack',
+    'gan_grad_unpack': 'data-parallel wire format: bit-equal to one fp32 multiply by test_gpu_elementwise::test_grad_pack_unpack',
     'gan_conv_stack_launch': 'layer stacks (conv.stack, off by default; out of scope)',
     'gan_norm_stats_partial': 'norm.fin_in_apply only (off by default; out of scope)',
     'gan_norm_finalize_act_fwd': 'norm.fin_in_apply only (off by default; out of scope)',
