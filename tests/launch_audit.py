@@ -1,7 +1,9 @@
-"""Launch audit of a captured training step (helper of tests/test_gpu_launch_audit.py; not a conftest).
+"""Launch audit of a captured training step and of the inference forward (helper of tests/test_gpu_launch_audit.py and
+tests/test_gpu_eval_audit.py; not a conftest).
 
-record(): every library call the step's capture body makes (Ctx.capture_graph's fn: the eager warm-up step is left out), with the
-descriptors the step itself built.  replay(): the recorded calls re-issued one at a time, in recorded order, on one stream; before
+record(): every library call the step's capture body makes (Ctx.capture_graph's fn: the eager warm-up step is left out), or an
+eager call makes inside Recorder.recording() (the inference calls: nothing of them is captured), with the descriptors the product
+code itself built.  replay(): the recorded calls re-issued one at a time, in recorded order, on one stream; before
 each call the regions it reads and writes are snapshot through the HIP runtime torch loaded (gan_amd/_lib.py: one runtime per
 process), after it the outputs are read back and compared with an fp64 reference computed from the snapshot - so no error
 compounds across layers and every gate is a rounding bound of that one call (GATES below).
@@ -10,6 +12,7 @@ Every recorded entry point either has a checker here or is named in ALLOWLIST wi
 neither fails the audit."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import re
@@ -75,6 +78,13 @@ ALLOWLIST = {
     'gan_loss_scale_update': 'fp16 loss-scale state machine: test_gpu_configs::test_loss_scale_state_machine',
     'gan_grad_pack': 'data-parallel wire format: bit-equal to the bf16 round-to-nearest-even cast by test_gpu_elementwise::test_grad_pack_unpack',
     'gan_grad_unpack': 'data-parallel wire format: bit-equal to one fp32 multiply by test_gpu_elementwise::test_grad_pack_unpack',
+    'gan_tile_gather_u8': 'uint8 source -> typed tiles through the normalize table: bit-equal to lut[src] of every tile (origins pulled '
+                          'back at the edges, a column window, sub-ranges of tiles, pad channels as gan_pack leaves them) for f32 / bf16 / '
+                          'f16 by test_gpu_tiles::test_gather_is_bit_exact_and_leaves_the_pad_channels_as_pack_does',
+    'gan_tile_blend': 'hat-weighted blend of the tiles: every pixel against the fp64 reference tests/tile_ref.py (gate 1e-5) by '
+                      'test_gpu_tiles::test_blend_matches_the_fp64_reference; split launches bit-equal to one launch, and nothing outside '
+                      'the covered pixels written, by test_split_launches_and_repeated_calls_give_the_same_bits / '
+                      'test_a_launch_owns_only_the_pixels_its_tiles_cover',
     'gan_conv_stack_launch': 'layer stacks (conv.stack, off by default; out of scope)',
     'gan_norm_stats_partial': 'norm.fin_in_apply only (off by default; out of scope)',
     'gan_norm_finalize_act_fwd': 'norm.fin_in_apply only (off by default; out of scope)',
@@ -278,7 +288,7 @@ class _Wrap:
 
 class Recorder:
     """Wraps the gan_* entry points of the loaded library (before the step object is built: the op lists hold the bound functions)
-    and records the calls made while Ctx.capture_graph runs its body."""
+    and records the calls made while Ctx.capture_graph runs its body, or inside `with rec.recording():` around an eager call."""
 
     def __init__(self, monkeypatch):
         self.lib = L.load()
@@ -290,6 +300,15 @@ class Recorder:
             fn = getattr(self.lib, name)
             self.orig[name] = fn
             monkeypatch.setattr(self.lib, name, _Wrap(self, name, fn))
+
+    @contextlib.contextmanager
+    def recording(self):
+        """Record the calls an eager piece of product code makes (an inference call: call.infer(fold=True), infer_tiled, ...)."""
+        was, self.active = self.active, True
+        try:
+            yield self
+        finally:
+            self.active = was
 
     def hook_capture(self, monkeypatch):
         """Record inside the body of every Ctx.capture_graph (patched on the class: an instance attribute would tie the context into a
@@ -309,9 +328,25 @@ class Recorder:
         monkeypatch.setattr(Ctx, 'capture_graph', capture_graph)
 
 
+def _nets_of(obj):
+    """[(tag, net)] of a step object (nets()), or of an inference call / model object (or a list of them), which hold one `.net`."""
+    if hasattr(obj, 'nets'):
+        nets = obj.nets()
+        tags = ['G', 'D'] if len(nets) == 2 else ['Gg', 'Gf', 'Dx', 'Dy'][:len(nets)]
+        return list(zip(tags, nets))
+    out = []
+    for o in obj if isinstance(obj, (list, tuple)) else [obj]:
+        net = getattr(o, 'net', None)
+        if net is not None and all(net is not n for _, n in out):
+            out.append(('G' if type(net).__name__ == 'GeneratorNet' else 'D', net))
+    return out
+
+
 def label_calls(calls, step):
     """Layer label of every call: the op tuple that holds its descriptor (label + shape), and the network tensor its weight /
-    gradient pointer lies in."""
+    gradient pointer lies in.  `step`: a step object, or an inference call / model object (or a list of them): these have no nets();
+    their weights are the network's NK copies (P.tr / P.nat) or the folded ones (FoldedParams.nk), and their fold call is given the
+    tensors it must leave alone (Call.guards: the master, nat, tr and the moving statistics, check_fold)."""
     by_addr = {}
     seen = set()
 
@@ -337,10 +372,14 @@ def label_calls(calls, step):
                 walk(e, depth + 1)
     walk(step)
     ranges = []
-    nets = step.nets() if hasattr(step, 'nets') else []
-    tags = ['G', 'D'] if len(nets) == 2 else ['Gg', 'Gf', 'Dx', 'Dy'][:len(nets)]
-    for tag, net in zip(tags, nets):
+    folds = {}
+    for tag, net in _nets_of(step):
         P = net.params
+        Fo = net.__dict__.get('_folded')
+        if Fo is not None:
+            for name, t in Fo.nk.items():
+                ranges.append((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), f"{tag}.{name}.folded"))
+            folds[Fo._table.data_ptr()] = (f"{tag} fold", [P.master] + list(P.nat.values()) + list(P.tr.values()) + list(P.state.values()))
         for name, (o, shape) in P.entries.items():
             n = int(np.prod(shape))
             for which in ('master', 'grad', 'm', 'v'):
@@ -356,6 +395,9 @@ def label_calls(calls, step):
                 return nm
         return ''
     for c in calls:
+        if c.name == 'gan_bn_fold_multi' and c.args[0] in folds:
+            c.label, c.guards = folds[c.args[0]]
+            continue
         obj = getattr(c.args[0], '_obj', None) if c.args else None
         lab = by_addr.get(C.addressof(obj), '') if obj is not None else ''
         w = ''
@@ -377,6 +419,24 @@ def conv_plan(d, op):
     L.check(L.load().gan_conv_plan_info(C.byref(d), op, info), "conv_plan_info")
     ts = L.load().gan_conv_tap_shared(C.byref(d), op)
     return list(info), ts
+
+
+def conv_pre(op, x, w, bias, stride):
+    """(fp64 pre-activation output of a conv launch, fp32 accumulation bound of each of its elements): check_conv's reference, on
+    host tensors (x [n,h,w,c], w [16][rows][x.c], bias [rows] or None) so that tests/test_cpu_launch_audit.py can put models of the
+    kernel - a right one and wrong ones - through the very gate the device values go through."""
+    ref = conv_ref(op, x, w, stride)
+    S = abs_bound(x, w).expand_as(ref)
+    if bias is not None:
+        ref = ref + bias
+        S = S + bias.abs()
+    return ref, ACC * S
+
+
+def y_gate(ref, eacc, act, slope, ydt):
+    """(expected stored output, its gate) of a launch without a fused backward epilogue: check_conv's 'y' item."""
+    out = act_f(ref, act, slope)
+    return out, K_ULP * ulp(out, ydt) + eacc
 
 
 def check_conv(call):
@@ -427,16 +487,11 @@ def check_conv(call):
     res = {}
     y1 = View(d.y, ydt)
     yg = y1.dense()
-    ref = conv_ref(op, x, w, d.stride)
-    S = abs_bound(x, w).expand_as(ref)
+    ref, eacc = conv_pre(op, x, w, bias, d.stride)
     assert tuple(ref.shape) == (d.y.n, d.y.h, d.y.w, d.y.c), (call.name, tuple(ref.shape), (d.y.n, d.y.h, d.y.w, d.y.c))
-    if bias is not None:
-        ref = ref + bias
-        S = S + bias.abs()
-    eacc = ACC * S                                   # fp32 accumulation bound of each (pre-activation) output
     if bf is None:
-        out = act_f(ref, d.act, d.slope)
-        res['y'] = ratio(yg, out, K_ULP * ulp(out, ydt) + eacc)
+        out, gate = y_gate(ref, eacc, d.act, d.slope, ydt)
+        res['y'] = ratio(yg, out, gate)
         res['y untouched outside y.c'] = untouched(y0, y1, 0, d.y.c)
         if partials:
             G = d.stats_groups
@@ -753,7 +808,59 @@ def check_bias_grad(call):
     return {'dbias': ratio(read(dbias, dyp.c).double(), s, ACC * (dy.abs().sum((0, 1, 2)) + acc * db0.abs()))}
 
 
-CHECKERS = dict({k: check_conv for k in OPS}, gan_conv_wgrad=check_wgrad, gan_norm_stats=check_norm_stats,
+def fold_ref(master, gamma, beta, mean, var, eps, transposed, tdt):
+    """gan_bn_fold_multi of one entry in float32, one IEEE operation at a time (the kernel's contraction is off): master [16, A, B]
+    -> (bias [co], nk [16, co, pad8(ci)] of the storage type; padding columns zero).  transposed: a Conv2D kernel (HWIO: A = Cin,
+    B = Cout), else a Conv2DTranspose kernel (A = Cout, B = Cin)."""
+    # numpy float32 scalars-and-arrays arithmetic: every operation is one correctly rounded IEEE operation, none fused
+    master, gamma, beta, mean, var = (t.to(torch.float32).numpy() for t in (master, gamma, beta, mean, var))
+    s = gamma * (np.float32(1.0) / np.sqrt(var + np.float32(eps)))
+    bias = torch.from_numpy((beta - mean * s).astype(np.float32))
+    w = np.transpose(master, (0, 2, 1)) if transposed else master          # -> [tap][co][ci]
+    co, ci = w.shape[1], w.shape[2]
+    nk = torch.zeros((16, co, (ci + 7) // 8 * 8), dtype=tdt)
+    nk[..., :ci] = torch.from_numpy((w * s[None, :, None]).astype(np.float32)).to(tdt)
+    return bias, nk
+
+
+def _bits(t):
+    return t.contiguous().view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def bit_equal(got, ref):
+    """Gate entry of a value that must come out bit for bit: 0 or inf."""
+    return 0.0 if got.dtype == ref.dtype and got.shape == ref.shape and torch.equal(_bits(got), _bits(ref)) else math.inf
+
+
+def check_fold(call):
+    """gan_bn_fold_multi: the device table of GanFoldEntry decoded; bias and folded NK copy of every entry BIT-EQUAL to fold_ref of
+    the snapshot; the entry's inputs, and the tensors label_calls named (Call.guards: master, nat, tr, moving statistics), unchanged."""
+    table, n, tiles, dt, eps = call.args[:5]
+    call.plan = f"{n} entries, {tiles} tiles"
+    size = C.sizeof(L.GanFoldEntry)
+    raw = read(table, n * size, tdtype=torch.uint8).numpy().tobytes()
+    ents = [L.GanFoldEntry.from_buffer_copy(raw[i * size:(i + 1) * size]) for i in range(n)]
+    pre = []
+    for e in ents:
+        co = e.B if e.transposed else e.A
+        pre.append([read(e.master, 16 * e.A * e.B)] + [read(p, co) for p in (e.gamma, e.beta, e.moving_mean, e.moving_var)])
+    guards = getattr(call, 'guards', [])
+    g0 = [_bits(t).clone() for t in guards]
+    yield
+    res = {'bias': 0.0, 'nk': 0.0, 'inputs unchanged': 0.0}
+    for e, p0 in zip(ents, pre):
+        co, ci = (e.B, e.A) if e.transposed else (e.A, e.B)
+        p1 = [read(e.master, 16 * e.A * e.B)] + [read(p, co) for p in (e.gamma, e.beta, e.moving_mean, e.moving_var)]
+        res['inputs unchanged'] = max([res['inputs unchanged']] + [bit_equal(a, b) for a, b in zip(p1, p0)])
+        bias, nk = fold_ref(p0[0].reshape(16, e.A, e.B), p0[1], p0[2], p0[3], p0[4], eps, e.transposed, TDT[dt])
+        res['bias'] = max(res['bias'], bit_equal(read(e.bias, co), bias))
+        res['nk'] = max(res['nk'], bit_equal(read(e.nk, nk.numel(), dt), nk.reshape(-1)))
+    if guards:
+        res['master / nat / tr / state unchanged'] = 0.0 if all(torch.equal(_bits(t), b) for t, b in zip(guards, g0)) else math.inf
+    return res
+
+
+CHECKERS = dict({k: check_conv for k in OPS}, gan_bn_fold_multi=check_fold, gan_conv_wgrad=check_wgrad, gan_norm_stats=check_norm_stats,
                 gan_norm_stats_finalize=check_norm_stats, gan_norm_act_fwd=check_norm_act_fwd, gan_norm_act_bwd=check_norm_act_bwd,
                 gan_norm_act_bwd_fused=check_norm_act_bwd, gan_act_bwd=check_act_bwd, gan_bias_grad=check_bias_grad)
 

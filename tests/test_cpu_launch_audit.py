@@ -4,8 +4,15 @@
   - plan coverage: the plan class of every convolution / wgrad launch in the table of plan_classes() (the captured one-GPU Pix2Pix
     and CycleGAN steps at channels = 1, see there) at B = 1..16 (256x256) and B = 1..8 (512x512, BASELINE config 4's per-GPU batch),
     from the host-side planners, must be reached by a batch the GPU audit runs.  A planner change that creates a class no audited
-    batch reaches fails here and names the batch sizes that reach it."""
+    batch reaches fails here and names the batch sizes that reach it;
+  - the same for the inference forward (eval_plan_classes(): the BatchNorm generator and PatchGAN in eval mode, every BatchNorm
+    layer one convolution with bias + activation; tests/test_gpu_eval_audit.py) at B = 1..64 (256x256) and B = 1..16 (512x512);
+  - the gate of check_conv and the bit-equality of check_fold must be able to fail: a float32 model of convolution + bias +
+    activation + rounding to storage sits inside the gate, the wrong variants a kernel could plausibly compute (a bias from the
+    neighbouring channel / channel group / parity column, dropped on the second half of the columns, activation before the bias,
+    the wrong activation or slope; in the fold eps outside the root, an unscaled moving mean, the other layout) land >= 2x outside."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -215,3 +222,211 @@ def test_audited_batches_reach_every_plan_class():
             if cls not in audited:
                 missing.append(f"{model} {S}x{S}: class {cls} ({where[0][1]}) reached at B = {[b for b, _ in where]}, audited {AUDITED[key]}")
     assert not missing, "plan classes no audited batch reaches:\n" + "\n".join(missing)
+
+
+# ---- plan coverage of the inference forward ------------------------------------------------------------------------------------
+# tests/test_gpu_eval_audit.py's bf16 cases: (network, size) -> batches.  The smallest sets that reach every class of the sweep
+# below (the batches people use: tools/bench_infer.py reports 16 and 64, --batch-size sets the predict batch, infer_tiled runs one
+# call per tile count and one for the last chunk).
+EVAL_AUDITED = {('generator', 256): (1, 8, 33, 49), ('generator', 512): (2, 9, 11),
+                ('discriminator', 256): (4, 11, 18, 33), ('discriminator', 512): (1, 5, 6, 9)}
+EVAL_SWEEP = {('generator', 256): range(1, 65), ('generator', 512): range(1, 17),
+              ('discriminator', 256): range(1, 65), ('discriminator', 512): range(1, 17)}
+
+
+def eval_launches(net, B, S, dt=L.BF16):
+    """[(tag, op, plan info, tap-shared, bias present, activation)] of the convolution launches of one eval forward, with the
+    views (channel slices of the concat buffers, their real pitches), bias and activation that nets.GenEvalCall / nets.DiscEvalCall
+    give them at channels = 1: no statistics, no fused epilogue requests."""
+    lib = L.load()
+    out = []
+
+    def V(n, h, c, pitch=None):
+        return L.GanTensor(16, n, h, h, c, pitch or c)
+
+    def conv(tag, op, x, y, stride=2, bias=True, act=L.ACT_NONE, y_f32=0):
+        d = L.GanConvDesc(dt, stride, x, y, 16, y.c, 16 if bias else None, act, 0.3, y_f32, 16, 1 << 40, None, 0, 0, None, None)
+        info = (C.c_int32 * 5)()
+        assert lib.gan_conv_plan_info(C.byref(d), op, info) == 0, tag
+        out.append((tag, op, list(info), lib.gan_conv_tap_shared(C.byref(d), op), bool(bias), act))
+
+    if net == 'generator':
+        hs = [S >> (i + 1) for i in range(8)]
+        pitch = [G_UP[j] + G_DOWN[6 - j] for j in range(7)]                  # concat buffer j: [up j | down 6-j]
+
+        def a_down(i):
+            return V(B, hs[i], 512) if i == 7 else V(B, hs[i], G_DOWN[i], pitch[6 - i])
+        conv("G.down0", 0, V(B, S, 8), a_down(0), bias=False, act=L.ACT_LRELU)
+        for i in range(1, 8):
+            conv(f"G.down{i}", 0, a_down(i - 1), a_down(i), act=L.ACT_LRELU)
+        for j in range(7):
+            x = V(B, hs[7], 512) if j == 0 else V(B, hs[7 - j], pitch[j - 1])
+            conv(f"G.up{j}", 2, x, V(B, hs[6 - j], G_UP[j], pitch[j]), act=L.ACT_RELU)
+        conv("G.last", 2, V(B, hs[0], pitch[6]), V(B, S, CH, 8), act=L.ACT_TANH)
+    else:
+        s1, s2, s3 = S // 2, S // 4, S // 8
+        s4, s5 = s3 - 1, s3 - 2
+        conv("D.down0", 0, V(B, S, 8), V(B, s1, 64), bias=False, act=L.ACT_LRELU)
+        conv("D.down1", 0, V(B, s1, 64), V(B, s2, 128), act=L.ACT_LRELU)
+        conv("D.down2", 0, V(B, s2, 128), V(B, s3, 256), act=L.ACT_LRELU)
+        conv("D.conv", 0, V(B, s3, 256), V(B, s4, 512), 1, act=L.ACT_LRELU)
+        conv("D.last", 0, V(B, s4, 512), V(B, s5, 1), 1, y_f32=1)
+    return out
+
+
+def eval_plan_classes(net, B, S, dt=L.BF16):
+    """{class: tag}: the class key of plan_classes (op, tile, split or not, parity form, statistics, tap sharing) plus (bias
+    present, activation)."""
+    return {('conv', op, info[0], info[1], info[2] > 1, info[3], '-', ts, bias, act): tag
+            for tag, op, info, ts, bias, act in reversed(eval_launches(net, B, S, dt))}
+
+
+def eval_plan_strings(net, B, S, dt=L.BF16):
+    """The launches as tests/test_gpu_eval_audit.py names what it recorded: check_conv's plan string + bias + activation.  The GPU
+    test fails if the set it saw differs from this one, so a change in nets.py cannot leave the table above behind."""
+    return {f"op{op} tile {info[0]}x{info[1]} split {info[2]} par {info[3]} stats {info[4]} ts {ts} bias {int(bias)} act {act}"
+            for tag, op, info, ts, bias, act in eval_launches(net, B, S, dt)}
+
+
+def eval_missing(audited):
+    missing = []
+    for key, batches in EVAL_SWEEP.items():
+        net, S = key
+        reach = {}
+        for B in batches:
+            for cls, tag in eval_plan_classes(net, B, S).items():
+                reach.setdefault(cls, []).append((B, tag))
+        seen = set()
+        for B in audited[key]:
+            seen |= set(eval_plan_classes(net, B, S))
+        for cls, where in reach.items():
+            if cls not in seen:
+                missing.append(f"{net} {S}x{S}: class {cls} ({where[0][1]}) reached at B = {[b for b, _ in where]}, audited {audited[key]}")
+    return missing
+
+
+@pytest.mark.skipif(not HAVE_LIB, reason="library not built")
+def test_eval_audited_batches_reach_every_plan_class():
+    missing = eval_missing(EVAL_AUDITED)
+    assert not missing, "plan classes of the eval forward no audited batch reaches:\n" + "\n".join(missing)
+    # the test can fail: without its largest batch a set leaves a class out, and the message names the batches that reach it
+    for key, batches in EVAL_AUDITED.items():
+        less = eval_missing({**EVAL_AUDITED, key: batches[:-1]})
+        assert less and all(f"{key[0]} {key[1]}x" in m and str(batches[-1]) in m for m in less), (key, less)
+
+
+# ---- the gates must be able to fail ----------------------------------------------------------------------------------------------
+ROUND = {L.F32: torch.float32, L.BF16: torch.bfloat16, L.F16: torch.float16}
+PCOLS = 64            # channels per parity block of columns of a parity-form tile (conv_gemm.hip: BN / 4 of the 128x256 family)
+
+
+def _case(op, dt, seed=5):
+    """2 x 8 x 8 input, 64 -> 256 channels, stored operands (values of the storage type), calibrated-style bias (non-zero,
+    different from channel to channel, both signs) -> x, w [16][256][64], bias, all fp64."""
+    g = torch.Generator().manual_seed(seed + op)
+    x = (torch.randint(0, 256, (2, 8, 8, 64), generator=g).float() / 127.5 - 1.0).to(ROUND[dt]).double()
+    w = (0.03 * torch.randn((16, 256, 64), generator=g)).to(ROUND[dt]).double()
+    bias = (0.2 * torch.randn(256, generator=g) + 0.3 * (torch.rand(256, generator=g) - 0.5)).float().double()
+    return x, w, bias
+
+
+def _model(op, x, w, bias, act, slope, dt, variant=None):
+    """float32 model of one launch: fp32 accumulation of the products of the stored operands, + bias, activation, one rounding to
+    storage.  variant: what a wrong kernel would compute instead."""
+    f = torch.float32
+    acc = A.conv_ref(op, x.to(f), w.to(f), 2)                        # [n, h, w, 256], fp32 sums
+    b = bias.to(f)
+    bb = b.expand_as(acc)
+    if variant == 'bias rotated by one channel':
+        bb = torch.roll(b, 1).expand_as(acc)
+    elif variant == 'bias rotated by one 4-channel group':
+        bb = torch.roll(b, 4).expand_as(acc)
+    elif variant == 'bias dropped on columns >= 128':
+        bb = torch.where(torch.arange(256) < 128, b, torch.zeros_like(b)).expand_as(acc)
+    elif variant == "bias of the other parity's column":             # the column index taken without % PCOLS (transposed form)
+        bb = torch.empty_like(acc)
+        for par in range(4):
+            idx = torch.arange(256) + par * PCOLS
+            bp = torch.where(idx < 256, b[idx.clamp(max=255)], torch.zeros_like(b))
+            bb[:, par >> 1::2, par & 1::2, :] = bp
+    a_, sl = act, slope
+    if variant == 'ReLU for LeakyReLU':
+        a_ = L.ACT_RELU
+    elif variant == 'slope 0.2 for 0.3':
+        sl = 0.2
+    if variant == 'activation before the bias':
+        out = A.act_f(acc, a_, sl) + bb
+    else:
+        out = A.act_f(acc + bb, a_, sl)
+    return out.to(f).to(ROUND[dt])
+
+
+CONV_VARIANTS = ['bias rotated by one channel', 'bias rotated by one 4-channel group', 'bias dropped on columns >= 128',
+                 'activation before the bias', 'ReLU for LeakyReLU', 'slope 0.2 for 0.3']
+
+
+@pytest.mark.parametrize('dt', [L.BF16, L.F16, L.F32], ids=['bf16', 'f16', 'f32'])
+@pytest.mark.parametrize('op', [0, 2], ids=['conv_fwd', 'convT_fwd'])
+def test_conv_gate_passes_the_float32_model_and_rejects_wrong_epilogues(op, dt):
+    x, w, bias = _case(op, dt)
+    ref, eacc = A.conv_pre(op, x, w, bias, 2)
+    out, gate = A.y_gate(ref, eacc, L.ACT_LRELU, 0.3, dt)
+    assert tuple(out.shape) == ((2, 4, 4, 256) if op == 0 else (2, 16, 16, 256))
+    assert float((ref < 0).double().mean()) > 0.2 and float((ref > 0).double().mean()) > 0.2       # both sides of the kink in use
+    good = A.ratio(_model(op, x, w, bias, L.ACT_LRELU, 0.3, dt), out, gate)
+    print(f"conv op{op} dtype {dt}: float32 model worst error / gate {good:.3f}")
+    assert good <= 1.0
+    if dt != L.F32:
+        assert good <= 0.55                      # half an ulp of the rounding to storage against a gate of one
+    variants = CONV_VARIANTS + (["bias of the other parity's column"] if op == 2 else [])
+    for v in variants:
+        r = A.ratio(_model(op, x, w, bias, L.ACT_LRELU, 0.3, dt, v), out, gate)
+        print(f"  {v}: {r:.1f}")
+        assert r >= 2.0, (v, r)
+    # ReLU layers (up0-6): LeakyReLU in their place, and the bias variants again
+    out, gate = A.y_gate(ref, eacc, L.ACT_RELU, 0.3, dt)
+    assert A.ratio(_model(op, x, w, bias, L.ACT_RELU, 0.3, dt), out, gate) <= 1.0
+    assert A.ratio(_model(op, x, w, bias, L.ACT_LRELU, 0.3, dt), out, gate) >= 2.0
+    for v in variants[:4] + variants[6:]:
+        assert A.ratio(_model(op, x, w, bias, L.ACT_RELU, 0.3, dt, v), out, gate) >= 2.0, v
+
+
+def _fold_inputs(A_, B_, transposed, seed):
+    rng = np.random.default_rng(seed)
+    co = B_ if transposed else A_
+    master = (0.05 * rng.standard_normal((16, A_, B_))).astype(np.float32)
+    gamma = (rng.uniform(0.6, 1.4, co) * rng.choice([-1.0, 1.0], co, p=[0.2, 0.8])).astype(np.float32)
+    beta = rng.normal(0.0, 0.2, co).astype(np.float32)
+    mean = rng.normal(0.0, 0.5, co).astype(np.float32)
+    var = rng.uniform(0.01, 3.0, co).astype(np.float32)
+    return master, gamma, beta, mean, var
+
+
+@pytest.mark.parametrize('dt', [L.BF16, L.F16, L.F32], ids=['bf16', 'f16', 'f32'])
+def test_fold_reference_is_the_numpy_fold_and_rejects_wrong_folds(dt):
+    from oracle import gan_oracle as O
+    from tests.inference_ref import _np_fold
+    tdt = ROUND[dt]
+    for k, (A_, B_, tr) in enumerate([(64, 256, 1), (256, 64, 0), (12, 70, 1), (96, 20, 0), (64, 64, 1)]):
+        master, gamma, beta, mean, var = _fold_inputs(A_, B_, tr, 20 + k)
+        t = [torch.from_numpy(a) for a in (master, gamma, beta, mean, var)]
+        bias, nk = A.fold_ref(*t, O.BN_EPS, tr, tdt)
+        co, ci = (B_, A_) if tr else (A_, B_)
+        assert tuple(nk.shape) == (16, co, (ci + 7) // 8 * 8) and not nk[..., ci:].any()
+        s_np, b_np, w_np = _np_fold(master, gamma, beta, mean, var, tr)          # tests/inference_ref.py: numpy, one operation at a time
+        assert A.bit_equal(bias, torch.from_numpy(b_np)) == 0.0
+        assert A.bit_equal(nk[..., :ci], torch.from_numpy(w_np).to(tdt)) == 0.0
+        # wrong folds: each must differ in at least one bit (check_fold's items are bit equality: any difference is outside)
+        eps = np.float32(O.BN_EPS)
+        s_eps = gamma * (np.float32(1.0) / (np.sqrt(var) + eps))                                 # eps outside the root
+        w3 = master.transpose(0, 2, 1) if tr else master
+        assert A.bit_equal(bias, torch.from_numpy(beta - mean * s_eps)) == math.inf
+        assert A.bit_equal(nk[..., :ci], torch.from_numpy(w3 * s_eps[None, :, None]).to(tdt)) == math.inf
+        assert A.bit_equal(bias, torch.from_numpy(beta - mean)) == math.inf                      # the moving mean left unscaled by s
+        swapped = master if tr else master.transpose(0, 2, 1)                                    # the other layout, same bytes count
+        if A_ == B_:
+            wrong = torch.from_numpy(swapped * s_np[None, :, None]).to(tdt)
+            assert A.bit_equal(nk[..., :ci], wrong) == math.inf
+        elif ci % 8 == 0:
+            wrong = torch.from_numpy(np.ascontiguousarray(swapped)).to(tdt).reshape(-1)          # what the buffer would hold, read flat
+            assert A.bit_equal(nk.reshape(-1), wrong) == math.inf
