@@ -9,13 +9,19 @@ process), after it the outputs are read back and compared with an fp64 reference
 compounds across layers and every gate is a rounding bound of that one call (GATES below).
 
 Every recorded entry point either has a checker here or is named in ALLOWLIST with the reason it is not checked; a call that has
-neither fails the audit."""
+neither fails the audit.
+
+Data-parallel step (tests/test_gpu_ddp_audit.py): IdentitySync is a GradSync of world 2 whose exchange does nothing - the "sum over
+ranks" is this rank's own wire contents, so Adam's 1/world halves every update; WireAudit follows the bf16 wire buffers through the
+compute calls (who wrote which element, exactly once); AdamEnd checks m, v, master and the NK copies of whole networks after the
+Adam graphs' calls; replay(check=...) leaves the calls the one-GPU audit already covers unchecked."""
 from __future__ import annotations
 
 import contextlib
 import ctypes as C
 import math
 import re
+import time
 
 import numpy as np
 import torch
@@ -58,10 +64,13 @@ ALLOWLIST = {
     'gan_adam_begin': 'step counter + lr_t scalar: within one ulp of the extended-precision value at t = 1..100,000 and kept on a skipped '
                       'step by test_gpu_elementwise::test_adam_begin; read back here as the input of every fused-Adam check',
     'gan_adam_tf': 'Adam of the norm / bias vectors (no planner choice): m, v, p per element against fp64 (cap-crossing count, wire '
-                   'gradient, scale state, skipped step) by test_gpu_elementwise::test_adam_tf',
+                   'gradient, scale state, skipped step) by test_gpu_elementwise::test_adam_tf; data-parallel step: every vector element '
+                   'against fp64 after the Adam graphs (AdamEnd.check)',
     'gan_adam_prepare_multi': 'the flat multi-tensor Adam + NK refresh: bit-equal to gan_adam_tf + gan_weights_prepare (both checked by '
                               'test_gpu_elementwise) in test_gpu_ops::test_fused_adam_prepare_equals_adam_then_prepare; '
-                              'the NK copies it writes are the weights every later conv reads, decoded from the device here',
+                              'the NK copies it writes are the weights every later conv reads, decoded from the device here; data-parallel '
+                              'step (segment tables, wire gradient, grad_scale 1/world): every kernel element and NK copy after the Adam '
+                              'graphs (AdamEnd.check)',
     'gan_weights_prepare_multi': 'NK copies of the master: bit-equal to the cast master in both layouts, padding zeroed, by '
                                  'test_gpu_elementwise::test_weights_prepare_multi; decoded from the device copy by every conv check here',
     'gan_pack': 'fp32 -> storage cast of the inputs: bit-equal to round-to-nearest-even on ties, overflow, subnormals, inf, NaN by '
@@ -76,8 +85,11 @@ ALLOWLIST = {
     'gan_grads_check': 'fp16 inf/nan flag of the loss scale: one inf / nan at the first, last (second trip) and a middle element by '
                        'test_gpu_elementwise::test_grads_check; the state machine by test_gpu_configs::test_loss_scale_state_machine',
     'gan_loss_scale_update': 'fp16 loss-scale state machine: test_gpu_configs::test_loss_scale_state_machine',
-    'gan_grad_pack': 'data-parallel wire format: bit-equal to the bf16 round-to-nearest-even cast by test_gpu_elementwise::test_grad_pack_unpack',
-    'gan_grad_unpack': 'data-parallel wire format: bit-equal to one fp32 multiply by test_gpu_elementwise::test_grad_pack_unpack',
+    'gan_grad_pack': 'data-parallel wire format: bit-equal to the bf16 round-to-nearest-even cast by test_gpu_elementwise::test_grad_pack_unpack; '
+                     'in a data-parallel capture (replay(wire=...)) its RANGE is recorded by check_pack_range: every element of the wire '
+                     'buffers written exactly once, by a direct wgrad or by a pack (WireAudit.coverage)',
+    'gan_grad_unpack': 'data-parallel wire format: bit-equal to one fp32 multiply by test_gpu_elementwise::test_grad_pack_unpack; the fp16 '
+                       'data-parallel step: the whole unpacked buffer bit-equal to wire * 1/world in AdamEnd.check',
     'gan_tile_gather_u8': 'uint8 source -> typed tiles through the normalize table: bit-equal to lut[src] of every tile (origins pulled '
                           'back at the edges, a column window, sub-ranges of tiles, pad channels as gan_pack leaves them) for f32 / bf16 / '
                           'f16 by test_gpu_tiles::test_gather_is_bit_exact_and_leaves_the_pad_channels_as_pack_does',
@@ -293,6 +305,7 @@ class Recorder:
     def __init__(self, monkeypatch):
         self.lib = L.load()
         self.calls, self.active = [], False
+        self.graph_starts = []
         self.orig = {}
         for name in L.SYMBOLS:
             if name in QUERIES:
@@ -319,6 +332,7 @@ class Recorder:
 
         def capture_graph(ctx, fn, *a, **k):
             def body():
+                rec.graph_starts.append(len(rec.calls))          # one entry per captured graph, in capture order
                 rec.active = True
                 try:
                     fn()
@@ -619,29 +633,57 @@ def _norm_fuse_fwd(d, nf, pre, out0, ref, eacc, yg, dt):
     return res
 
 
-def check_wgrad(call):
-    d = call.args[0]._obj
-    dt = d.dtype
+def wgrad_plan(d):
+    """check_wgrad's plan string from the host planner alone."""
     info = (C.c_int32 * 4)()
     L.check(L.load().gan_wgrad_plan_info(C.byref(d), info), "wgrad_plan_info")
+    return f"wgrad tile {info[0]}x{info[1]} split {info[2]} fold {info[3]}" + (" adam_fuse" if d.adam_fuse else "") + \
+        (" acc" if d.accumulate else "") + (f" conc{d.concurrent}" if d.concurrent else "") + (" wire" if d.dw_wire else "")
+
+
+def wire_gate(ref, eg):
+    """Gate of a gradient stored in the bf16 wire format: the audit's gate of any stored 16-bit value."""
+    return K_ULP * ulp(ref, L.BF16) + eg
+
+
+def check_wgrad(call):
+    """gan_conv_wgrad against the fp64 wgrad_ref of the operands it read, in each of its three forms:
+      - plain: dw (+= with accumulate) within the fp32 gate;
+      - GanAdamFuse: dw untouched, m / v / master against fp64 Adam of the reference gradient, the NK copies bit-equal to the cast
+        master;
+      - dw_wire (data-parallel step, Pix2PixStep._capture_bucketed): the launch's last kernel writes the gradient as bf16 at this
+        kernel's offset of the exchange's wire buffer.  Same reference, the gate of a stored 16-bit value (wire_gate); dw must keep
+        its bits, and so must every element of the wire buffers outside [offset, offset + 16 * big_c * small_c) - the whole
+        buffers are compared on the device (WireAudit), which covers the neighbouring kernels and the ALIGN padding on both
+        sides.  A launch without dw_wire in a data-parallel capture must leave the wire buffers alone altogether."""
+    d = call.args[0]._obj
+    dt = d.dtype
     af = L.GanAdamFuse.from_address(d.adam_fuse) if d.adam_fuse else None
-    call.plan = f"wgrad tile {info[0]}x{info[1]} split {info[2]} fold {info[3]}" + (" adam_fuse" if af else "") + \
-        (" acc" if d.accumulate else "") + (f" conc{d.concurrent}" if d.concurrent else "")
-    if d.dw_wire:
-        raise AssertionError("dw_wire launches are out of the audit's scope (multi-rank)")
+    call.plan = wgrad_plan(d)
+    wa = _WIRE
+    if d.dw_wire and wa is None:
+        raise AssertionError("a dw_wire launch needs the wire buffers it writes into: replay(..., wire=WireAudit(...))")
     big, small = View(d.big, dt).dense(), View(d.small, dt).dense()
     n = 16 * d.big_c * d.small_c
     dw0 = read(d.dw, n)
     if af is not None:
         p0, m0, v0 = read(af.master, n).double(), read(af.m, n).double(), read(af.v, n).double()
+    if wa is not None:
+        wi, woff = wa.owner(d.dw_wire) if d.dw_wire else (None, 0)
+        w0 = wa.snapshot()
     yield
     res = {}
     g = wgrad_ref(big, small, d.stride, d.big_c, d.small_c).reshape(-1)
-    # sum|terms| <= max|big| * sum over positions of |small| per small channel (the cheap bound: an exact |big| x |small| pass would
-    # double the reference's cost)
-    sb = float(big[..., :d.big_c].abs().max()) * small[..., :d.small_c].abs().sum((0, 1, 2))
-    eg = ACC * sb.expand(16, d.big_c, d.small_c).reshape(-1)
+    eg = wgrad_acc_bound(big, small, d.big_c, d.small_c)
     dw1 = read(d.dw, n)
+    if wa is not None:
+        res.update(wa.written(w0, wi, woff, woff + n if d.dw_wire else woff))
+    if d.dw_wire:
+        res['dw untouched'] = 0.0 if torch.equal(dw0.view(torch.int32), dw1.view(torch.int32)) else math.inf
+        got = read(d.dw_wire, n, L.BF16)
+        res['wire'] = ratio(got, g, wire_gate(g, eg))
+        res['wire rounding bias'] = rounding_bias(got, g)
+        return res
     if af is None:
         acc = float(d.accumulate)
         ref = g + acc * dw0.double()
@@ -865,6 +907,240 @@ CHECKERS = dict({k: check_conv for k in OPS}, gan_bn_fold_multi=check_fold, gan_
                 gan_norm_act_bwd_fused=check_norm_act_bwd, gan_act_bwd=check_act_bwd, gan_bias_grad=check_bias_grad)
 
 
+def plan_of(call):
+    """The plan string a checker gives `call`, from the descriptor and the host-side planner queries alone: nothing is read from the
+    device and nothing is issued (replay asserts that every checker agrees with it).  '' for entry points without a checker."""
+    n, a = call.name, call.args
+    if n in OPS:
+        d, op = a[0]._obj, OPS[n]
+        info, ts = conv_plan(d, op)
+        full = info[4] == -1 and bool(d.norm_fuse)
+        return f"op{op} tile {info[0]}x{info[1]} split {info[2]} par {info[3]} stats {info[4]} ts {ts}" + \
+            (" bwd_fuse" if d.bwd_fuse else "") + (" norm_fuse" if full else "")
+    if n == 'gan_conv_wgrad':
+        return wgrad_plan(a[0]._obj)
+    if n in ('gan_norm_stats', 'gan_norm_stats_finalize'):
+        return f"groups {a[0]._obj.groups}" + (f" chunks {a[1]}" if n == 'gan_norm_stats_finalize' else "")
+    if n == 'gan_norm_act_fwd':
+        d = a[0]._obj
+        return f"groups {d.groups} act {d.act}" + (" dropout" if d.dropmask else "")
+    if n in ('gan_norm_act_bwd', 'gan_norm_act_bwd_fused'):
+        d = a[0]._obj
+        return f"groups {d.groups}" + (f" fused chunks {a[1]}" if n == 'gan_norm_act_bwd_fused' else
+                                       f" act {d.act}" + (" dropout" if d.dropmask else ""))
+    if n == 'gan_act_bwd':
+        d = a[0]._obj
+        return f"act {d.act}" + (" dbias" if d.dbias else "")
+    if n == 'gan_bias_grad':
+        return "acc" if a[3] else ""
+    if n == 'gan_bn_fold_multi':
+        return f"{a[1]} entries, {a[2]} tiles"
+    return ''
+
+
+# ---- data-parallel step: an exchange that does nothing, the wire buffers, the update of whole networks ---------------------------
+SENTINEL = 0x7FA5            # a bf16 NaN no kernel produces: what the wire buffers hold before the compute calls
+_WIRE = None                 # the WireAudit of the replay in progress (replay(wire=...))
+
+
+def identity_sync(step, compress):
+    """A GradSync of world 2 for ONE process: pack / unpack are the real kernels, the exchange is the identity (start returns no
+    handle, wait does nothing; no process group, no child process, no RCCL).  The "sum over ranks" is this rank's own wire
+    contents (own fp32 gradients for compress = False), so the 1/world of the mean is real and visible: every update is half the
+    one-GPU update."""
+    from gan_amd.ddp import GradSync
+
+    class IdentitySync(GradSync):
+        def start(self, i, lo=0, hi=None):
+            return None
+
+        def wait(self, handle):
+            pass
+
+    s = IdentitySync([n.params.grad for n in step.nets()], compress_bf16=compress, lib=step.ctx.lib)
+    s.world, s.active = 2, True
+    return s
+
+
+class WireAudit:
+    """The bf16 wire buffers of a data-parallel capture (GradSync.wire, one per network, ParamSet offsets), compared whole and on
+    the device around every call that may write them: which elements changed, that none of them lies outside the call's range,
+    and that no element changes twice.  fill() plants SENTINEL; coverage() after the last compute call: every element of every
+    kernel's and vector's real extent written exactly once, no SENTINEL left inside one."""
+
+    def __init__(self, step, sync):
+        self.bufs = [w.view(torch.int16) for w in sync.wire]
+        self.sets = [n.params for n in step.nets()]
+        self.count = [torch.zeros(b.numel(), dtype=torch.int8, device=b.device) for b in self.bufs]
+        self.log = []            # (buffer, lo, hi) of every range a call claimed
+
+    def fill(self):
+        for b, c in zip(self.bufs, self.count):
+            b.fill_(SENTINEL)
+            c.zero_()
+        self.log.clear()
+        if self.bufs[0].is_cuda:
+            torch.cuda.synchronize()
+
+    def owner(self, ptr):
+        for i, b in enumerate(self.bufs):
+            if b.data_ptr() <= ptr < b.data_ptr() + 2 * b.numel():
+                return i, (ptr - b.data_ptr()) // 2
+        raise AssertionError(f"wire pointer {ptr:#x} lies in no wire buffer")
+
+    def snapshot(self):
+        return [b.clone() for b in self.bufs]
+
+    def written(self, before, i, lo, hi):
+        """Gate entries of one call that claimed elements [lo, hi) of buffer i (i None: nothing)."""
+        res = {'wire untouched outside its range': 0.0, 'no wire element written twice': 0.0}
+        for k, (b0, b1) in enumerate(zip(before, self.bufs)):
+            ch = b0 != b1
+            if k == i:
+                self.log.append((i, lo, hi))
+                self.count[k] += ch.to(torch.int8)
+                if bool((self.count[k][lo:hi] > 1).any()):
+                    res['no wire element written twice'] = math.inf
+                ch[lo:hi] = False
+            if bool(ch.any()):
+                res['wire untouched outside its range'] = math.inf
+        return res
+
+    def coverage(self):
+        """Failures (strings) of the exactly-once rule over the real extents."""
+        bad = []
+        for i, (P, b, c) in enumerate(zip(self.sets, self.bufs, self.count)):
+            for name, (o, shape) in P.entries.items():
+                n = int(np.prod(shape))
+                cnt, left = c[o:o + n], int((b[o:o + n] == SENTINEL).sum())
+                if left or bool((cnt != 1).any()):
+                    bad.append(f"wire {i} {name} [{o}, {o + n}): {int((cnt == 0).sum())} elements never written, "
+                               f"{int((cnt > 1).sum())} written twice, {left} still hold the sentinel")
+            if bool((c > 1).any()):
+                bad.append(f"wire {i}: {int((c > 1).sum())} elements (padding included) written by more than one call")
+        return bad
+
+
+def check_pack_range(call):
+    """gan_grad_pack in a data-parallel capture: its range is recorded (WireAudit), nothing outside it may change, and - it costs
+    nothing here - the range must equal torch's round-to-nearest-even cast of the fp32 gradients it read."""
+    src, dst, n = call.args[:3]
+    wa = _WIRE
+    i, lo = wa.owner(dst)
+    call.plan = f"wire {i} [{lo}, {lo + n})"
+    g = wa.sets[i].grad
+    assert src == g.data_ptr() + 4 * lo, "gan_grad_pack reads another range than it writes"
+    w0 = wa.snapshot()
+    yield
+    res = wa.written(w0, i, lo, lo + n)
+    res['wire = rne(grad)'] = 0.0 if torch.equal(wa.bufs[i][lo:lo + n], g[lo:lo + n].to(torch.bfloat16).view(torch.int16)) else math.inf
+    return res
+
+
+def adam_end_ratios(p0, m0, v0, g, gs, lr_t, p1, m1, v1, b1=0.5, b2=0.999):
+    """{item: error / gate} of one Adam step over flat tensors (any device): m and v against fp64 of the stored inputs (g: the stored
+    gradient widened to fp32, gs: what the kernel multiplies it by), master against fp64 of the NEW moments the kernel stored, all
+    within tests/elementwise_ref.adam_gates."""
+    from tests import elementwise_ref as E
+    omb1, omb2, eps = (float(c) for c in E.adam_consts(b1, b2))
+    p0, m0, v0, g, p1, m1, v1 = (t.double() for t in (p0, m0, v0, g, p1, m1, v1))
+    gr = g * gs
+    mr, vr = m0 + (gr - m0) * omb1, v0 + (gr * gr - v0) * omb2
+    u = m1 * lr_t / (torch.sqrt(v1) + eps)
+    pr = p0 - u
+    gm, gv, gp = E.adam_gates(m0, v0, g, gs, pr, u)
+    return {'adam m': ratio(m1, mr, gm), 'adam v': ratio(v1, vr, gv), 'adam master': ratio(p1, pr, gp)}
+
+
+def rounding_bias(got, ref, dt=L.BF16):
+    """|mean over the elements of sign(ref) * (got - ref) / ulp(ref)| / 0.05.  Round-to-nearest-even leaves an error uniform in +-half
+    an ulp: over the n >= 65,536 elements of the smallest kernel a launch writes in the wire format its mean has a standard deviation
+    of 0.29 / sqrt(n) <= 0.0012 ulp (the fp32 accumulation error is symmetric too), so 0.05 is forty of them; truncation leaves -0.5.
+    The per-element gate (one ulp) cannot tell the two apart."""
+    ref = ref.double()
+    e = torch.sign(ref) * (got.double() - ref) / ulp(ref, dt)
+    nz = ref != 0
+    if not bool(torch.isfinite(e).all()):
+        return math.inf
+    return abs(float(e[nz].mean())) / 0.05 if bool(nz.any()) else 0.0
+
+
+def wgrad_acc_bound(big, small, big_c, small_c):
+    """fp32 accumulation bound of every element of a kernel gradient: ACC * sum|terms|, sum|terms| <= max|big| * sum over positions of
+    |small| per small channel (the cheap bound: an exact |big| x |small| pass would double the reference's cost)."""
+    sb = float(big[..., :big_c].abs().max()) * small[..., :small_c].abs().sum((0, 1, 2))
+    return ACC * sb.expand(16, big_c, small_c).reshape(-1)
+
+
+class AdamEnd:
+    """The update of every network as a whole, after the Adam graphs' calls of a data-parallel step.
+    snapshot() before the first of them: master, m, v and the gradient source - the bf16 wire buffer (g = wire / world), the fp32
+    gradient buffer (fp32 wire: g = grad * grad_scale) or, on fp16, nothing yet: there g is the buffer gan_grad_unpack leaves, which
+    must be bit-equal to wire * 1/world.  check(): m, v, master of every parameter element against fp64 on the device (torch
+    float64) within tests/elementwise_ref.adam_gates - u and p from the stored new moments, as the fused-Adam check does - step == 1,
+    the gradient source untouched, every NK copy bit-equal to the cast master with zero padding, the kernels' ALIGN padding of
+    master / m / v untouched; fp16: loss scale unchanged and the step taken."""
+
+    def __init__(self, step, sync, b1=0.5, b2=0.999):
+        self.step, self.sync, self.b1, self.b2 = step, sync, b1, b2
+        self.mode = 'wire' if step._wire_adam() else ('unpack' if sync.compress else 'fp32')
+
+    def snapshot(self):
+        ctx = self.step.ctx
+        self.pre = []
+        for i, net in enumerate(self.step.nets()):
+            P = net.params
+            src = self.sync.wire[i] if self.mode != 'fp32' else P.grad
+            self.pre.append((P.master.clone(), P.m.clone(), P.v.clone(), src.clone()))
+        self.ls0 = ctx.ls.clone() if ctx.ls is not None else None
+        torch.cuda.synchronize()
+
+    def check(self):
+        ctx, world = self.step.ctx, self.sync.world
+        rows = []
+        for i, (net, (p0, m0, v0, src0)) in enumerate(zip(self.step.nets(), self.pre)):
+            P = net.params
+            res = {}
+            src1 = self.sync.wire[i] if self.mode != 'fp32' else P.grad
+            if self.mode == 'wire':
+                g, gs = src0.float(), 1.0 / world
+                res['wire untouched by Adam'] = 0.0 if torch.equal(src0.view(torch.int16), src1.view(torch.int16)) else math.inf
+            elif self.mode == 'fp32':
+                g, gs = src0, self.sync.grad_scale
+                assert gs == 1.0 / world
+                res['grad untouched by Adam'] = 0.0 if torch.equal(src0.view(torch.int32), src1.view(torch.int32)) else math.inf
+            else:
+                g, gs = P.grad.clone(), self.sync.grad_scale * float(self.ls0[1])
+                res['unpacked grad = wire * 1/world'] = 0.0 if torch.equal(g.view(torch.int32), (src0.float() * (1.0 / world)).view(torch.int32)) else math.inf
+                res['gradient finite'] = 0.0 if bool(torch.isfinite(g).all()) else math.inf
+            real = torch.zeros(P.total, dtype=torch.bool, device=p0.device)
+            for name, (o, shape) in P.entries.items():
+                real[o:o + int(np.prod(shape))] = True
+            pad = ~real
+            pad[P.vec_start:] = False               # (gan_adam_tf runs over the vectors' padding too: harmless, not gated)
+            res['kernel padding of master / m / v untouched'] = 0.0 if all(
+                torch.equal(a[pad].view(torch.int32), b[pad].view(torch.int32)) for a, b in ((p0, P.master), (m0, P.m), (v0, P.v))) else math.inf
+            res.update(adam_end_ratios(*(t[real] for t in (p0, m0, v0, g)), gs, float(P.lr_t[0]),
+                                       *(t[real] for t in (P.master, P.m, P.v)), self.b1, self.b2))
+            p1, p0 = P.master[real], p0[real]
+            res['step == 1'] = 0.0 if int(P.step[0]) == 1 else math.inf
+            nk = 0.0
+            for name in P.nat:
+                o, shape = P.entries[name]
+                A_, B_ = shape[2], shape[3]
+                w = P.master[o:o + 16 * A_ * B_].view(16, A_, B_)
+                for t, ref, c in ((P.nat[name], w, B_), (P.tr[name], w.transpose(1, 2), A_)):
+                    if not torch.equal(_bits(t[..., :c]), _bits(ref.to(t.dtype))) or bool(t[..., c:].any()):
+                        nk = math.inf
+            res['nat / tr = cast(master), padding zero'] = nk
+            if self.ls0 is not None:
+                res['loss scale unchanged, step taken'] = 0.0 if (float(ctx.ls[0]) == float(self.ls0[0]) and float(ctx.ls[3]) == 0.0
+                                                                  and not torch.equal(p1, p0)) else math.inf
+            tag = _nets_of(self.step)[i][0]
+            rows.append((f"{tag} whole network ({int(real.sum())} parameters)", 'gan_adam (whole network)', f"{self.mode} g, scale {gs:g}", '', res))
+        return rows
+
+
 def _short(sym):
     m = re.match(r'_Z(?:N\d*)?(\d+)', sym)
     if not m:
@@ -873,22 +1149,44 @@ def _short(sym):
     return sym[m.end():m.end() + n]
 
 
-def replay(calls, stream=None):
+AS_ONE_GPU = 'as in the one-GPU step'
+TIMES = []                   # (seconds, label, entry point) of every call of the last replays: where a case's time goes
+
+
+def replay(calls, stream=None, check=None, wire=None):
     """Re-issue the recorded calls in order on one stream, each checked against its reference.  Returns rows
-    (label, entry point, plan, kernels, {item: error/gate}) - None for allowlisted entry points."""
+    (label, entry point, plan, kernels, {item: error/gate}) - None for allowlisted entry points.
+    check: a predicate of a call - a call it rejects is issued unchecked and its row's plan reads AS_ONE_GPU (its entry point must
+    still have a checker or an ALLOWLIST entry).  wire: the WireAudit of a data-parallel capture - gan_grad_pack then has its range
+    recorded (check_pack_range), whatever the predicate says, and every wgrad launch is held to the wire buffers."""
+    global _WIRE
     lib = L.load()
     stream = stream or torch.cuda.current_stream()
     st = stream.cuda_stream
     rows = []
+    _WIRE = wire
     for c in calls:
         chk = CHECKERS.get(c.name)
         if chk is None and c.name not in ALLOWLIST:
+            _WIRE = None
             raise AssertionError(f"{c.name} ({c.label}) has neither a reference in tests/launch_audit.py nor an ALLOWLIST entry")
+        if wire is not None and c.name == 'gan_grad_pack':
+            chk = check_pack_range
+        elif chk is not None and check is not None and not check(c):
+            chk = None
         torch.cuda.synchronize()
+        t_call = time.time()
         c.plan = ''
         gen = chk(c) if chk is not None else None
         if gen is not None:
-            next(gen)                                           # snapshot
+            try:
+                next(gen)                                       # snapshot
+            except BaseException:
+                _WIRE = None
+                raise
+            assert c.name == 'gan_grad_pack' or c.plan == plan_of(c), (c.name, c.plan, plan_of(c))
+        elif c.name in CHECKERS:
+            c.plan = AS_ONE_GPU
         L.check(lib.gan_set_option(b'diag.launch_log', 1), "launch log")
         rc = c.fn(*c.args[:-1], st)
         torch.cuda.synchronize()
@@ -903,6 +1201,8 @@ def replay(calls, stream=None):
             except StopIteration as e:
                 res = e.value
         rows.append((c.label, c.name, c.plan, ','.join(dict.fromkeys(syms)), res))
+        TIMES.append((time.time() - t_call, c.label, c.name))
+    _WIRE = None
     return rows
 
 
@@ -910,7 +1210,7 @@ def table(rows, title=''):
     lines = [f"== launch audit {title}: {len(rows)} calls"]
     for lab, name, plan, ks, res in rows:
         if res is None:
-            lines.append(f"  {lab[:44]:44s} {name[4:]:22s} allowlisted")
+            lines.append(f"  {lab[:44]:44s} {name[4:]:22s} {plan if plan == AS_ONE_GPU else 'allowlisted'}")
             continue
         worst = max(res.items(), key=lambda kv: kv[1]) if res else ('-', 0.0)
         lines.append(f"  {lab[:44]:44s} {name[4:]:22s} {plan:50s} {ks[:70]:70s} {worst[0]} {worst[1]:.3f}")
@@ -919,6 +1219,16 @@ def table(rows, title=''):
 
 def failures(rows):
     return [(lab, name, plan, k, v) for lab, name, plan, ks, res in rows if res for k, v in res.items() if not v <= 1.0]
+
+
+def worst_per_item(rows, name):
+    """{item: worst error / gate} over the rows of one entry point."""
+    w = {}
+    for lab, nm, plan, ks, res in rows:
+        if res and nm == name:
+            for k, v in res.items():
+                w[k] = max(w.get(k, 0.0), v)
+    return w
 
 
 def worst_per_entry(rows):

@@ -87,8 +87,14 @@ def T(n, h, c):
     return L.GanTensor(16, n, h, h, c, c)
 
 
-def plan_classes(model, B, S, dt=L.BF16):
+def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None):
     """{class: label} of every conv / wgrad launch of one captured step.
+    ddp: None - the one-GPU step; 'direct' - the data-parallel Pix2Pix step on its bucketed schedule with the bf16 wire
+    (Pix2PixStep._capture_bucketed): every wgrad launch is given its place in the wire buffer and writes it where
+    gan_wgrad_wire_direct says it can; 'plain' - every other data-parallel schedule (fp32 wire, ddp_wire_direct = False, the phased
+    schedules of Pix2Pix and CycleGAN): plain-write wgrad launches.  The data-parallel launches carry neither GanAdamFuse nor
+    accumulate (CycleGAN's wide wgrads write), the convolutions, `concurrent` and the wide 3B operands are those of the one-GPU step.
+    strings: a set that receives the wgrad plan strings as launch_audit.check_wgrad writes them (the GPU cases compare).
     Pix2Pix: G at B images (wgrads on a side lane: concurrent 1); D forward per invocation (B images, the captured schedule) and
     batched (2B, two BatchNorm groups); D's parameter pass over 2B, its input pass (dgrads + the dx dgrad into the generator's
     gradient) over B; D wgrads concurrent 0.
@@ -123,9 +129,17 @@ def plan_classes(model, B, S, dt=L.BF16):
         out.setdefault(('conv', op, info[0], info[1], info[2] > 1, info[3], st, ts), tag)
 
     def wgrad(tag, big, small, big_c, small_c, stride, conc):
-        d = L.GanWgradDesc(dt, stride, big, small, 16, big_c, small_c, 0, 16, 1 << 40, conc, None)
+        d = L.GanWgradDesc(dt, stride, big, small, 16, big_c, small_c, 0, 16, 1 << 40, conc, None, 64 if ddp == 'direct' else None)
+        wire = 0
+        if d.dw_wire:
+            wire = lib.gan_wgrad_wire_direct(C.byref(d))
+            assert wire in (0, 1), tag
+            if not wire:
+                d.dw_wire = None                     # (as nets._Builder.wgrad does)
         assert lib.gan_wgrad_plan_info(C.byref(d), winfo) == 0, tag
-        out.setdefault(('wgrad', winfo[0], winfo[1], winfo[2] > 1, winfo[3]), tag)
+        out.setdefault(('wgrad', winfo[0], winfo[1], winfo[2] > 1, winfo[3], wire), tag)
+        if strings is not None:
+            strings.add(A.wgrad_plan(d))
 
     hs = [S >> (i + 1) for i in range(8)]
     cin_up = [512] + [G_UP[j - 1] + G_DOWN[7 - j] for j in range(1, 7)]          # channels of up j's input (a7 / cat[j-1])
@@ -430,3 +444,237 @@ def test_fold_reference_is_the_numpy_fold_and_rejects_wrong_folds(dt):
         elif ci % 8 == 0:
             wrong = torch.from_numpy(np.ascontiguousarray(swapped)).to(tdt).reshape(-1)          # what the buffer would hold, read flat
             assert A.bit_equal(nk.reshape(-1), wrong) == math.inf
+
+
+# ---- plan coverage of the data-parallel step ---------------------------------------------------------------------------------------
+# tests/test_gpu_ddp_audit.py's cases: name -> (model, dtype, wgrad table of plan_classes, per-rank batches), all 256x256 (the
+# smallest size the 8-level generator accepts).  A case's wgrad launches are the table's at its batch; the batches of all cases that
+# share a table must together reach every wgrad class of per-rank batches 1..8 (DDP_SWEEP).  The sweep's answer: batches 1..3 reach
+# five of the six classes of every table, and the sixth - the 256 x 256 ping-pong kernel, which only D's stride-1 layer at 2B >= 8
+# images takes - needs B >= 4; B = 4 alone reaches all six.  So one case per table runs B = 4 (no 512x512 case: nothing is left for
+# it) and every other case, which adds no class, the cheapest batch, 1.
+DDP_CASES = {
+    'pix2pix-bf16-bucketed-wire-direct': ('pix2pix', 'bf16', 'direct', (4,)),
+    'pix2pix-bf16-bucketed-wire-pack': ('pix2pix', 'bf16', 'plain', (1,)),
+    'pix2pix-bf16-bucketed-fp32-wire': ('pix2pix', 'bf16', 'plain', (4,)),
+    'pix2pix-f16-phased': ('pix2pix', 'f16', 'plain', (1,)),
+    'cyclegan-bf16-phased-wire': ('cyclegan', 'bf16', 'plain', (4,)),
+    'pix2pix-bf16-phased-wire': ('pix2pix', 'bf16', 'plain', (1,)),
+}
+DDP_SWEEP = range(1, 9)
+DDP_DT = {'bf16': L.BF16, 'f16': L.F16}
+
+
+def ddp_audited(cases=None):
+    """(model, table) -> the batches of the 16-bit cases that run it."""
+    out = {}
+    for model, dtype, tab, batches in (cases or DDP_CASES).values():
+        out[(model, tab)] = tuple(sorted(set(out.get((model, tab), ()) + tuple(batches))))
+    return out
+
+
+DDP_AUDITED = ddp_audited()
+
+
+def ddp_wgrad_classes(model, tab, B, dt=L.BF16):
+    return {k: v for k, v in plan_classes(model, B, 256, dt, ddp=tab).items() if k[0] == 'wgrad'}
+
+
+def ddp_wgrad_plan_strings(model, dtype, tab, B):
+    """The wgrad launches of a data-parallel capture as launch_audit.check_wgrad names them (the GPU cases compare)."""
+    s = set()
+    plan_classes(model, B, 256, DDP_DT[dtype], ddp=tab, strings=s)
+    return s
+
+
+def ddp_missing(audited):
+    missing = []
+    for (model, tab), batches in audited.items():
+        reach = {}
+        for B in DDP_SWEEP:
+            for cls, tag in ddp_wgrad_classes(model, tab, B).items():
+                reach.setdefault(cls, []).append((B, tag))
+        seen = set()
+        for B in batches:
+            seen |= set(ddp_wgrad_classes(model, tab, B))
+        for cls, where in reach.items():
+            if cls not in seen:
+                missing.append(f"{model} {tab} 256x256: class {cls} ({where[0][1]}) reached at B = {[b for b, _ in where]}, audited {batches}")
+    return missing
+
+
+@pytest.mark.skipif(not HAVE_LIB, reason="library not built")
+def test_ddp_audited_batches_reach_every_plan_class():
+    assert {(m, t) for m, _, t, _ in DDP_CASES.values()} == set(DDP_AUDITED)
+    missing = ddp_missing(DDP_AUDITED)
+    assert not missing, "wgrad classes of the data-parallel step no audited batch reaches:\n" + "\n".join(missing)
+    # f16 plans its wgrads as bf16 does (the planner only tells 16-bit from fp32): the f16 case adds no class of its own
+    for B in DDP_SWEEP:
+        assert set(ddp_wgrad_classes('pix2pix', 'plain', B, L.F16)) == set(ddp_wgrad_classes('pix2pix', 'plain', B, L.BF16)), B
+    # the direct table has launches that write the wire format and launches that cannot (tap-folded first / last layers, the logits)
+    wires = {k[5] for B in DDP_AUDITED[('pix2pix', 'direct')] for k in ddp_wgrad_classes('pix2pix', 'direct', B)}
+    assert wires == {0, 1}
+    # the test can fail: without its largest batch a set leaves a class out, and the message names the batches that reach it; and
+    # no smaller batch than that one would do
+    for key, batches in DDP_AUDITED.items():
+        less = ddp_missing({key: batches[:-1]})
+        assert less and all(f"{key[0]} {key[1]} 256x" in m and str(batches[-1]) in m for m in less), (key, less)
+        assert all(ddp_missing({key: (b,)}) for b in range(1, batches[-1])), key
+
+
+# ---- the data-parallel gates must be able to fail ------------------------------------------------------------------------------------
+# A numpy float32 model of what the bucketed step does to ONE flat buffer: two kernels (64 -> 128 channels, small tensor 2 x 8 x 8)
+# whose wgrad launches write the bf16 wire format themselves (split-K in 4 slabs, fp32 sums, round to nearest even), a vector of 100
+# elements (padded to ALIGN) that gan_grad_pack casts, then Adam from the wire with grad_scale = 1/2 - put through the very objects
+# the GPU audit uses (launch_audit.WireAudit, wire_gate, rounding_bias, adam_end_ratios).
+ALIGN = 64
+KN = 16 * 64 * 128
+VEC, VEC_PAD = 100, 128
+LAYOUT = {'k0.kernel': (0, (4, 4, 64, 128)), 'k1.kernel': (KN, (4, 4, 64, 128)), 'v.gamma': (2 * KN, (VEC,))}
+TOTAL = 2 * KN + VEC_PAD
+DDP_VARIANTS = ['truncation instead of RNE', 'wire written one 4-element group late', "wire written at the neighbouring kernel's offset",
+                'one split-K slab dropped', 'grad_scale 1', 'grad_scale 1/4', 'Adam reads the stale fp32 buffer for one kernel',
+                'a kernel missing from its segment', 'a kernel updated twice', 'pack range stops ALIGN short',
+                'pack range overlaps a direct kernel']
+
+
+class _FlatSet:
+    ALIGN = ALIGN
+    entries, total, vec_start = LAYOUT, TOTAL, 2 * KN
+
+    def __init__(self, grad):
+        self.grad = grad
+
+
+class _FlatNet:
+    def __init__(self, grad):
+        self.params = _FlatSet(grad)
+
+
+class _FlatStep:
+    def __init__(self, grad):
+        self._nets = (_FlatNet(grad),)
+
+    def nets(self):
+        return self._nets
+
+
+class _FlatSync:
+    def __init__(self):
+        self.wire = [torch.zeros(TOTAL, dtype=torch.bfloat16)]
+
+
+def _bf16_trunc(x):
+    return (x.contiguous().view(torch.int32) & -65536).view(torch.float32).to(torch.bfloat16)
+
+
+def _ddp_inputs(seed):
+    g = torch.Generator().manual_seed(seed)
+    big = (torch.randint(0, 256, (2, 16, 16, 64), generator=g).float() / 127.5 - 1.0).to(torch.bfloat16)
+    small = (0.05 * torch.randn((2, 8, 8, 128), generator=g)).to(torch.bfloat16)
+    return big, small
+
+
+def _wgrad_f32(big, small, drop_slab=False):
+    """fp32 model of a split launch: 4 slabs over the 128 output positions, each an fp32 GEMM, summed in fp32."""
+    cols = F_unfold(big.float())                                     # [M = 128, 16 * 64]
+    sm = small.float().reshape(-1, 128)
+    out = torch.zeros((16 * 64, 128), dtype=torch.float32)
+    for k in range(1 if drop_slab else 0, 4):
+        sl = slice(32 * k, 32 * k + 32)
+        out = out + cols[sl].t() @ sm[sl]
+    return out.reshape(-1)
+
+
+def F_unfold(big):
+    """[n, 16, 16, c] -> [n * 8 * 8, 16 taps * c]: the stride-2, pad-1, 4 x 4 patches, tap-major as dw[tap][big channel]."""
+    n, h, w, c = big.shape
+    p = torch.nn.functional.unfold(A.nchw(big), kernel_size=4, stride=2, padding=1)          # [n, c * 16, 64]
+    return p.reshape(n, c, 16, 64).permute(0, 3, 2, 1).reshape(n * 64, 16 * c)
+
+
+def _ddp_model(variant=None):
+    """Run the model (or a wrong variant) through the audit's objects -> {item: worst error / gate}."""
+    from tests import elementwise_ref as E
+    g = torch.Generator().manual_seed(23)
+    grad = torch.zeros(TOTAL)                                        # fp32 gradient buffer: the direct kernels leave it at zero
+    grad[2 * KN:2 * KN + VEC] = 0.3 * torch.randn(VEC, generator=g)
+    sync = _FlatSync()
+    wa = A.WireAudit(_FlatStep(grad), sync)
+    wa.fill()
+    wire = sync.wire[0]
+    res = {}
+
+    def note(d):
+        for k, v in d.items():
+            res[k] = max(res.get(k, 0.0), v)
+    ops = [_ddp_inputs(31), _ddp_inputs(32)]
+    for k, (big, small) in enumerate(ops):                           # the two direct wgrad launches
+        acc = _wgrad_f32(big, small, drop_slab=(variant == 'one split-K slab dropped' and k == 0))
+        out = _bf16_trunc(acc) if variant == 'truncation instead of RNE' else acc.to(torch.bfloat16)
+        lo = k * KN
+        at = lo
+        if k == 0 and variant == 'wire written one 4-element group late':
+            at = lo + 4
+        if k == 0 and variant == "wire written at the neighbouring kernel's offset":
+            at = KN
+        w0 = wa.snapshot()
+        wire[at:at + KN] = out
+        note(wa.written(w0, 0, lo, lo + KN))
+        ref = A.wgrad_ref(big.double(), small.double(), 2, 64, 128).reshape(-1)
+        eg = A.wgrad_acc_bound(big.double(), small.double(), 64, 128)
+        got = wire[lo:lo + KN].clone()
+        note({'wire': A.ratio(got, ref, A.wire_gate(ref, eg)), 'wire rounding bias': A.rounding_bias(got, ref)})
+    lo, hi = 2 * KN, TOTAL                                           # gan_grad_pack: the rest of the bucket
+    if variant == 'pack range stops ALIGN short':
+        hi -= ALIGN
+    if variant == 'pack range overlaps a direct kernel':
+        lo -= ALIGN
+    w0 = wa.snapshot()
+    wire[lo:hi] = grad[lo:hi].to(torch.bfloat16)
+    note(wa.written(w0, 0, lo, hi))
+    res['coverage'] = math.inf if wa.coverage() else 0.0
+    # Adam of the whole buffer from the wire, grad_scale = 1 / world
+    p0 = 0.02 * torch.randn(TOTAL, generator=g)
+    m0 = 1e-4 * torch.randn(TOTAL, generator=g)
+    v0 = 1e-8 * torch.rand(TOTAL, generator=g) + 1e-10
+    lr_t = float(E.lr_t_model(2e-4, 0.5, 0.999, 1))
+    gs = {'grad_scale 1': 1.0, 'grad_scale 1/4': 0.25}.get(variant, 0.5)
+    src = wire.float().numpy()
+    if variant == 'Adam reads the stale fp32 buffer for one kernel':
+        src = src.copy()
+        src[KN:2 * KN] = grad[KN:2 * KN].numpy()
+    with np.errstate(invalid='ignore'):          # (a sentinel left in the wire is a NaN: the variant is meant to show it)
+        p1, m1, v1 = E.adam_model(p0.numpy(), m0.numpy(), v0.numpy(), src, lr_t, gs)
+    if variant == 'a kernel missing from its segment':
+        for a, b in ((p1, p0), (m1, m0), (v1, v0)):
+            a[KN:2 * KN] = b.numpy()[KN:2 * KN]
+    if variant == 'a kernel updated twice':
+        q = E.adam_model(p1[:KN], m1[:KN], v1[:KN], src[:KN], lr_t, gs)
+        for a, b in zip((p1, m1, v1), q):
+            a[:KN] = b
+    real = torch.zeros(TOTAL, dtype=torch.bool)
+    for o, shape in LAYOUT.values():
+        real[o:o + int(np.prod(shape))] = True
+    f = lambda a: torch.from_numpy(np.ascontiguousarray(a))[real]
+    note(A.adam_end_ratios(p0[real], m0[real], v0[real], wire.float()[real], 0.5, lr_t, f(p1), f(m1), f(v1)))
+    return res
+
+
+def test_ddp_gates_pass_the_float32_model_and_reject_wrong_variants():
+    good = _ddp_model()
+    print("data-parallel float32 model, worst error / gate: " + ', '.join(f"{k} {v:.3f}" for k, v in good.items()))
+    assert all(v <= 0.5 for v in good.values()), good
+    smallest = {}
+    for v in DDP_VARIANTS:
+        r = _ddp_model(v)
+        out = {k: x for k, x in r.items() if x >= 2.0}
+        print(f"  {v}: " + (', '.join(f"{k} {x:.1f}" for k, x in out.items()) or f"NOT SEEN ({r})"))
+        assert out, (v, r)
+        smallest[v] = max(out.values())
+    worst = min(smallest, key=smallest.get)
+    print(f"smallest ratio of a wrong variant: {smallest[worst]:.1f} ({worst})")
+    # truncation: the per-element gate of a stored 16-bit value is one ulp and passes it - only the rounding-bias item (and, for
+    # gan_grad_pack, the bit equality of check_pack_range) sees it
+    t = _ddp_model('truncation instead of RNE')
+    assert t['wire'] <= 1.0 and t['wire rounding bias'] >= 2.0
