@@ -919,3 +919,40 @@ extern "C" size_t gan_launch_log(char* buf, size_t cap) {
   }
   return all.size() + 1;
 }
+
+// ---- exponential moving average of a weight arena (include/gan_amd.h, gan_ema_update) -----------------------------------------
+// shadow += (param - shadow) * (1 - d_t), one float4 per thread and trip.  Every thread forms d_t itself from the launch-invariant
+// (decay, *step): in fp64, so that the fp32 value it is rounded to is the nearest one to the exact min(decay, (1 + t) / (10 + t))
+// for every t.  fmaf is spelled out: one rounded subtract, one fused multiply-add, whatever the contraction setting.
+__global__ __launch_bounds__(256) void ema_update_kernel(float4* __restrict__ shadow, const float4* __restrict__ param, long long nvec,
+                                                         float decay, const int32_t* step, float* decay_used) {
+  float d = decay;
+  if (step) {
+    const double t = (double)*step;
+    d = (float)fmin((double)decay, (1.0 + t) / (10.0 + t));
+  }
+  const float omd = 1.0f - d;
+  if (decay_used && blockIdx.x == 0 && threadIdx.x == 0) *decay_used = d;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long long)gridDim.x * 256) {
+    float4 s = shadow[i];
+    const float4 w = param[i];
+    s.x = fmaf(w.x - s.x, omd, s.x);
+    s.y = fmaf(w.y - s.y, omd, s.y);
+    s.z = fmaf(w.z - s.z, omd, s.z);
+    s.w = fmaf(w.w - s.w, omd, s.w);
+    shadow[i] = s;
+  }
+}
+
+extern "C" int gan_ema_update(float* shadow, const float* param, int64_t count, float decay, const int32_t* step, float* decay_used,
+                              gan_stream_t stream) {
+  if (!shadow || !param || count <= 0 || count % 4 || (((uintptr_t)shadow | (uintptr_t)param) & 15)) return GAN_E_ARG;
+  if (!(decay >= 0.f && decay < 1.f)) return GAN_E_ARG;
+  const long long nvec = count / 4;
+  long long blocks = (nvec + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  GAN_LAUNCH(ema_update_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float4*)shadow, (const float4*)param, nvec,
+             decay, step, decay_used);
+  GAN_CHECK_LAUNCH();
+  return 0;
+}

@@ -15,6 +15,7 @@ from . import data as D
 from . import ddp
 from .base_gan import GAN
 from .checkpoint import Checkpoint, CheckpointManager, latest_checkpoint
+from .ema import WeightAverage
 from .steps import CycleGANStep
 from .runner import Run, plot_loss_curves, run_epochs, save_panels
 from .utils import cyclegan_losses
@@ -38,6 +39,13 @@ class CycleGAN(GAN):
         self.dist = ddp.DistInfo(0, 1, self.config.get('device'))
         self._rng = np.random.default_rng(seed)
         self.sync = None
+        # moving averages of the two generators' weights: every replayed training step moves both
+        self.generator_g_ema = self.generator_f_ema = None
+        ema_decay = float(self.config.get('ema_decay', 0.0))
+        if ema_decay > 0 or str(self.config.get('predict_weights', 'raw')) == 'ema':
+            warmup = str(self.config.get('ema_warmup', 'true')) == 'true'
+            self.generator_g_ema = WeightAverage(self.generator_g, ema_decay, warmup)
+            self.generator_f_ema = WeightAverage(self.generator_f, ema_decay, warmup)
 
     def enable_data_parallel(self, info, wire='bf16', exchange='allreduce'):
         """As Pix2Pix.enable_data_parallel: one process per GPU, gradients of the four networks averaged over the ranks."""
@@ -118,6 +126,8 @@ class CycleGAN(GAN):
                               lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
                               seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=tuple(m.net for m in self._models()))
             st.sync = self.sync
+            if training and self.generator_g_ema is not None:
+                st.ema = (self.generator_g_ema, self.generator_f_ema)
             saved = [(ps, ps.master.clone(), ps.m.clone(), ps.v.clone(), ps.step.clone()) for ps in (m.net.params for m in self._models())]
             from .pix2pix import _step_state, _restore_step_state
             extra = _step_state(self.ctx, st)
@@ -224,6 +234,13 @@ def parse_opt(argv=None):
                         help="--train: 'host' decodes and augments every image on the CPU in every epoch; 'device' decodes each file once, "
                              "keeps the uint8 images in GPU memory and builds every batch there")
     parser.add_argument('--data-cache-gb', type=float, default=64, help='--data-cache device: most GiB of decoded images to keep per GPU')
+    parser.add_argument('--ema-decay', type=float, default=0.0,
+                        help='--train: keep exponential moving averages of the two generators\' weights with this decay, updated on '
+                             'the GPU after every step and saved with the checkpoint (0 = off; e.g. 0.999)')
+    parser.add_argument('--ema-warmup', type=str, default='true', choices=['true', 'false'],
+                        help="--ema-decay: 'true' = decay min(ema-decay, (1 + step) / (10 + step)), so that a young average follows the weights")
+    parser.add_argument('--predict-weights', type=str, default='raw', choices=['raw', 'ema'],
+                        help="--predict: 'raw' = the checkpoint's generator_g weights; 'ema' = its averaged weights (a run with --ema-decay)")
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')
@@ -231,6 +248,8 @@ def parse_opt(argv=None):
     parser.add_argument('--exchange', type=str, default='allreduce', choices=['allreduce', 'rs_ag'],
                         help='gradient exchange: one all-reduce per bucket, or fp32 reduce-scatter + all-gather in the wire format')
     args = parser.parse_args(argv)
+    if not 0.0 <= args.ema_decay < 1.0:
+        parser.error(f"--ema-decay {args.ema_decay} is outside [0, 1)")
     assert (args.img_size == 256) or (args.img_size == 512), "img-size currently only supported for 256 x 256 or 512 x 512 pixels!"
     assert (args.validation_size > 0.0 and args.validation_size <= 0.3), "validation size is a proportion and bounded between 0-0.3!"
     assert (args.test_img >= 1), "test-img is an integer and must be >=1!"
@@ -249,13 +268,22 @@ def main(opt):
         names = ('generator_g', 'generator_f', 'discriminator_x', 'discriminator_y')
         objects = {n: getattr(cgan, n) for n in names}
         objects.update({n + '_optimizer': getattr(cgan, n + '_optimizer') for n in names})
+        if cgan.generator_g_ema is not None:    # after the generators: an average that finds no weights of its own starts over from theirs
+            objects.update(generator_g_ema=cgan.generator_g_ema, generator_f_ema=cgan.generator_f_ema)
         checkpoint = Checkpoint(**objects)                     # object names of cycle_gan.py:437-444
         run.write_json('config.json', cgan.config)
         if opt.predict:
             if info.is_main:
                 dataset = cgan.image_pipeline(predict=True)[0]
                 checkpoint.restore(latest_checkpoint(opt.weights))
-                cgan.predict(dataset, run.root)
+                if opt.predict_weights == 'ema':
+                    if not cgan.generator_g_ema.loaded:
+                        raise SystemExit(f"--predict-weights ema: checkpoint holds no averaged weights ({opt.weights}); "
+                                         "train with --ema-decay")
+                    with cgan.generator_g_ema.averaged():
+                        cgan.predict(dataset, run.root)
+                else:
+                    cgan.predict(dataset, run.root)
         else:
             train_X, train_Y, val_X, val_Y, test = cgan.image_pipeline(predict=False)
             manager = (CheckpointManager(checkpoint, os.path.join(run.root, 'training_checkpoints'), max_to_keep=3)

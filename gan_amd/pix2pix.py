@@ -15,6 +15,7 @@ from . import ddp
 from . import tiling
 from .base_gan import GAN
 from .checkpoint import Checkpoint, CheckpointManager, latest_checkpoint
+from .ema import WeightAverage
 from .quality import QualityMeter, image_quality, summary
 from .steps import Pix2PixStep
 from .runner import Run, plot_loss_curves, run_epochs, save_panels
@@ -68,6 +69,11 @@ class Pix2Pix(GAN):
         self.dist = ddp.DistInfo(0, 1, self.config.get('device'))      # main() replaces it in a data-parallel run
         self._rng = np.random.default_rng(seed)
         self.sync = None          # gan_amd.ddp.GradSync for data-parallel training
+        # moving average of the generator weights: every replayed training step moves it
+        self.generator_ema = None
+        ema_decay = float(self.config.get('ema_decay', 0.0))
+        if ema_decay > 0 or str(self.config.get('predict_weights', 'raw')) == 'ema':
+            self.generator_ema = WeightAverage(self.generator, ema_decay, str(self.config.get('ema_warmup', 'true')) == 'true')
 
     def enable_data_parallel(self, info, wire='bf16', exchange='allreduce'):
         """One process per GPU (torchrun): gradients are averaged over the ranks with RCCL all-reduces overlapped with the
@@ -139,6 +145,8 @@ class Pix2Pix(GAN):
                              seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net),
                              generator_loss=self.config.get('generator_loss', 'l1'))
             st.sync = self.sync
+            if training and self.generator_ema is not None:
+                st.ema = (self.generator_ema,)
             saved = self._snapshot()       # capture() runs warm-up passes (they also move BatchNorm's moving statistics): undo them
             extra = _step_state(self.ctx, st)
             replay = st.capture(training=training)
@@ -146,6 +154,9 @@ class Pix2Pix(GAN):
             _restore_step_state(extra)
             self._steps[key] = (st, replay)
         return self._steps[key]
+
+    def _ema_active(self):
+        return self.generator_ema is not None and self.generator_ema.decay > 0
 
     def _snapshot(self):
         return [(ps, ps.master.clone(), ps.m.clone(), ps.v.clone(), ps.step.clone(), {k: v.clone() for k, v in ps.state.items()})
@@ -214,16 +225,24 @@ class Pix2Pix(GAN):
         if not self.dist.is_main:           # rank 0 alone writes checkpoints and sample images
             save = sample = (lambda *a: None)
         self.val_quality = {'SSIM': [], 'PSNR': [], 'MAE': []}
+        self.val_quality_ema = {'SSIM': [], 'PSNR': [], 'MAE': []}
         after_epoch = None
         if str(self.config.get('quality_metrics', 'false')) == 'true':
-            def after_epoch(epoch):     # validation set in inference mode; epoch means over all ranks' images, as the losses
+            def val_pass(into):         # validation set in inference mode; epoch means over all ranks' images, as the losses
                 meter = QualityMeter()
                 self._evaluate_into(meter, val_ds)
                 mean = ddp.mean_over_ranks(*meter.sums(), self.dist)
                 vals = mean.cpu().tolist() if mean is not None else [float('nan')] * 4
-                for k, v in zip(self.val_quality, vals):
-                    self.val_quality[k].append(v)
+                for k, v in zip(into, vals):
+                    into[k].append(v)
                 return f"val SSIM: {vals[0]:.4f}, PSNR: {vals[1]:.2f} dB, MAE: {vals[2]:.4f}"
+
+            def after_epoch(epoch):
+                line = val_pass(self.val_quality)
+                if self._ema_active():  # the same pass on the averaged weights
+                    with self.generator_ema.averaged():
+                        line += " | averaged weights: " + val_pass(self.val_quality_ema)
+                return line
         return run_epochs(self.config['epochs'], list(pix2pix_losses()), lambda: train_ds, lambda: val_ds, self.train_step,
                           save, sample, ('Generator Total Loss', 'Discriminator Loss'),
                           epoch_mean=lambda acc, n: ddp.mean_over_ranks(acc, n, self.dist),
@@ -334,6 +353,13 @@ def parse_opt(argv=None):
                         help="image quality of the generator against the ground truth (SSIM as tf.image.ssim, PSNR, MAE), computed on "
                              "the GPU: --train writes logs/val_quality.json (per epoch) and logs/test_quality.json, --predict "
                              "writes logs/prediction_metrics.json")
+    parser.add_argument('--ema-decay', type=float, default=0.0,
+                        help='--train: keep an exponential moving average of the generator weights with this decay, updated on the GPU '
+                             'after every step and saved with the checkpoint (0 = off; e.g. 0.999)')
+    parser.add_argument('--ema-warmup', type=str, default='true', choices=['true', 'false'],
+                        help="--ema-decay: 'true' = decay min(ema-decay, (1 + step) / (10 + step)), so that a young average follows the weights")
+    parser.add_argument('--predict-weights', type=str, default='raw', choices=['raw', 'ema'],
+                        help="--predict: 'raw' = the checkpoint's generator weights; 'ema' = its averaged weights (a run with --ema-decay)")
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')
@@ -348,6 +374,8 @@ def parse_opt(argv=None):
         parser.error("--generator-loss ssim is not supported by gan_amd (the reference's SSIM term compares input with target and "
                      "carries no gradient, pix2pix.py:182-184); use the default --generator-loss l1, or --generator-loss dssim "
                      "for 1 - SSIM(generated, target)")
+    if not 0.0 <= args.ema_decay < 1.0:
+        parser.error(f"--ema-decay {args.ema_decay} is outside [0, 1)")
     assert (args.img_size == 256) or (args.img_size == 512), "img-size currently only supported for 256 x 256 or 512 x 512 pixels!"
     if args.tile_overlap is None:
         args.tile_overlap = args.img_size // 4
@@ -372,14 +400,24 @@ def main(opt):
         p2p = Pix2Pix(vars(opt))
         if opt.train:
             p2p.enable_data_parallel(info, opt.wire, opt.exchange)
-        checkpoint = Checkpoint(generator_optimizer=p2p.generator_optimizer, discriminator_optimizer=p2p.discriminator_optimizer,
-                                generator=p2p.generator, discriminator=p2p.discriminator)
+        objects = dict(generator_optimizer=p2p.generator_optimizer, discriminator_optimizer=p2p.discriminator_optimizer,
+                       generator=p2p.generator, discriminator=p2p.discriminator)
+        if p2p.generator_ema is not None:      # after `generator`: restore runs in this order, and an average that finds no
+            objects['generator_ema'] = p2p.generator_ema     # weights of its own starts over from the restored generator
+        checkpoint = Checkpoint(**objects)
         run.write_json('config.json', p2p.config)
         if opt.predict:
             if info.is_main:
                 dataset, _, _ = p2p.image_pipeline(predict=True)
                 checkpoint.restore(latest_checkpoint(opt.weights))
-                metrics = p2p.predict(dataset, run.root)
+                if opt.predict_weights == 'ema':
+                    if not p2p.generator_ema.loaded:
+                        raise SystemExit(f"--predict-weights ema: checkpoint holds no averaged weights ({opt.weights}); "
+                                         "train with --ema-decay")
+                    with p2p.generator_ema.averaged():
+                        metrics = p2p.predict(dataset, run.root)
+                else:
+                    metrics = p2p.predict(dataset, run.root)
                 if metrics is not None:
                     run.write_json('prediction_metrics.json', summary(metrics))
         else:
@@ -392,6 +430,11 @@ def main(opt):
                 if opt.quality_metrics == 'true':
                     run.write_json('val_quality.json', {k: [v if np.isfinite(v) else None for v in vs] for k, vs in p2p.val_quality.items()})
                     run.write_json('test_quality.json', summary(p2p.evaluate(test)))
+                    if p2p._ema_active():
+                        run.write_json('val_quality_ema.json', {k: [v if np.isfinite(v) else None for v in vs]
+                                                                for k, vs in p2p.val_quality_ema.items()})
+                        with p2p.generator_ema.averaged():
+                            run.write_json('test_quality_ema.json', summary(p2p.evaluate(test)))
                 final = run.dir('final_test_imgs', fresh=True)
                 for k, (inp, tar) in enumerate(test.unbatch()):
                     p2p.generate_images(p2p.generator, inp[None], tar[None], os.path.join(final, f"img{k}.png"))

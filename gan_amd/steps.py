@@ -72,6 +72,7 @@ class _StepBase:
         self.l1_ws = torch.zeros(4096, dtype=torch.float32, device=ctx.device)
         self.bce_ws = torch.zeros(1024, dtype=torch.float32, device=ctx.device)
         self.sync = None             # GradSync for data-parallel runs
+        self.ema = ()                # WeightAverage objects (gan_amd/ema.py) a replayed training step moves, DESIGN.md section 15
         self._in_step = _InStepAdam()
 
     def _example_inputs(self):
@@ -166,13 +167,18 @@ class _StepBase:
     def _graph(self, fn):
         return self.ctx.capture_graph(fn, CAPTURE_MODE)      # (an exception inside leaves no forked lane behind: Ctx.capture_graph)
 
-    def _replayer(self, body):
-        """The callable that capture() returns: inputs -> the static buffers, body(), the losses."""
+    def _replayer(self, body, training):
+        """The callable that capture() returns: inputs -> the static buffers, body(), the losses.  A training step then moves the
+        weight averages attached to it (self.ema): one launch each on the stream the graph(s) were launched on, which every
+        schedule's body ends joined onto, so stream order puts it behind every Adam launch of the step - and outside every capture."""
         def replay(*inputs):
             for dst, src in zip(self._static_in, inputs):
                 if src is not dst:
                     dst.copy_(src, non_blocking=True)
             body()
+            if training:
+                for e in self.ema:
+                    e.update()
             return self.losses
         replay.inputs = self._static_in      # a caller that fills these buffers itself (and passes them back) skips the copies
         return replay
@@ -192,7 +198,7 @@ class _StepBase:
             self._prebuild_fused_adam()         # (op lists and device tables of the captured schedule: no uploads inside the capture)
         g1 = self._graph(lambda: self._run(*self._static_in, training=training, capturing=True))
         self._graphs = (g1, None, None)
-        return self._replayer(g1.replay)
+        return self._replayer(g1.replay, training)
 
     def _capture_phased(self, training):
         """Data-parallel schedule by PHASES (every step type has it; Pix2Pix bf16 prefers its finer bucketed schedule): the step is
@@ -256,7 +262,7 @@ class _StepBase:
                 A[0].replay()
             else:
                 ctx.join(cur, lane4)
-        return self._replayer(body)
+        return self._replayer(body, training)
 
 
 class Pix2PixStep(_StepBase):
@@ -564,7 +570,7 @@ class Pix2PixStep(_StepBase):
                     boundary(k - 1)
             boundary(len(G) - 1)
             ctx.join(cur, lane4)
-        return self._replayer(body)
+        return self._replayer(body, True)
 
     def train_step(self, input_image, target, training=True):
         """(gen_total_loss, gen_gan_loss, gen_l1_loss, disc_loss) as a 4-element device tensor view."""

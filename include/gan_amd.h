@@ -397,6 +397,15 @@ int gan_adam_tf(float* param, float* m, float* v, const void* grad, int64_t coun
 int gan_grads_check(const float* grad, int64_t count, float* scale_state, gan_stream_t stream);
 int gan_loss_scale_update(float* scale_state, int32_t growth_interval, float max_scale, gan_stream_t stream);
 
+/* Exponential moving average of a weight arena (no counterpart in the reference; tf.train.ExponentialMovingAverage's update):
+ * shadow <- shadow + (param - shadow) * (1 - d_t), per element as fmaf(param - shadow, 1 - d_t, shadow).
+ * d_t = decay if step == NULL, else min(decay, (1 + t) / (10 + t)) with t = *step (the num_updates form: a young average
+ * follows the weights closely); `step` is the device counter gan_adam_begin advances and is only read here.  decay_used
+ * (device, one float, may be NULL) receives d_t.  One streaming launch, no atomics, no workspace: the same inputs give the
+ * same bits.  count > 0 and a multiple of 4, both arrays 16-byte aligned, 0 <= decay < 1; otherwise GAN_E_ARG and no launch. */
+int gan_ema_update(float* shadow, const float* param, int64_t count, float decay, const int32_t* step, float* decay_used,
+                   gan_stream_t stream);
+
 /* ---- misc ----------------------------------------------------------------------------------- */
 /* Bernoulli(0.5) keep-mask from a counter hash of (seed, *step, stream_id, index). */
 int gan_dropout_mask(uint8_t* mask, int64_t count, uint64_t seed, const int32_t* step, uint32_t stream_id,
