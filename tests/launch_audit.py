@@ -14,7 +14,12 @@ neither fails the audit.
 Data-parallel step (tests/test_gpu_ddp_audit.py): IdentitySync is a GradSync of world 2 whose exchange does nothing - the "sum over
 ranks" is this rank's own wire contents, so Adam's 1/world halves every update; WireAudit follows the bf16 wire buffers through the
 compute calls (who wrote which element, exactly once); AdamEnd checks m, v, master and the NK copies of whole networks after the
-Adam graphs' calls; replay(check=...) leaves the calls the one-GPU audit already covers unchecked."""
+Adam graphs' calls; replay(check=...) leaves the calls the one-GPU audit already covers unchecked.
+
+RGB steps (tests/test_gpu_rgb_audit.py, channels = 3): thin_call() is the predicate of the calls that differ from the channels = 1
+step (an operand with <= 8 channels), conv_class() / wgrad_class() the plan class of a descriptor as the host tables of
+tests/test_cpu_launch_audit.py key it, missing_required() names the required calls no checked row holds, pad_channels() the
+image-side buffers whose padding channels are not bit-zero."""
 from __future__ import annotations
 
 import contextlib
@@ -159,6 +164,14 @@ class View:
         self.rows = t.n * t.h * t.w
         self.span = (self.rows - 1) * t.pitch + t.c if self.rows else 0
         self.raw = read(t.ptr, self.span, dt)
+
+    @classmethod
+    def of_host(cls, raw, t, dt):
+        """A snapshot made of a host tensor (the CPU models of tests/test_cpu_launch_audit.py): raw = the span's elements."""
+        v = cls.__new__(cls)
+        v.t, v.dt, v.rows, v.raw = t, dt, t.n * t.h * t.w, raw
+        v.span = raw.numel()
+        return v
 
     def dense(self):
         t = self.t
@@ -421,6 +434,8 @@ def label_calls(calls, step):
             w = owner(obj.dw) or (owner(L.GanAdamFuse.from_address(obj.adam_fuse).master) if obj.adam_fuse else '')
         elif isinstance(obj, (L.GanNormDesc, L.GanNormBwdDesc)):
             w = owner(obj.gamma)
+        elif c.name == 'gan_bias_grad':
+            w = owner(c.args[2])                 # (no descriptor: the bias whose gradient it writes)
         c.label = (w + ' ' + lab).strip() or c.name
 
 
@@ -467,7 +482,12 @@ def check_conv(call):
     ydt = L.F32 if d.y_f32 else dt
     xv = View(d.x, dt)
     x = xv.dense()
-    w = read(d.w, 16 * d.w_rows * d.x.c, dt).double().reshape(16, d.w_rows, d.x.c)[:, :d.y.c]
+    # rows [0, y.c) of every tap: the extent the kernels read.  (D's dx dgrad is given a pointer advanced by some rows into the
+    # operand: whole [16][w_rows] tables from there would end that many rows behind the allocation.)
+    nw = (15 * d.w_rows + d.y.c) * d.x.c
+    w = torch.zeros(16 * d.w_rows * d.x.c, dtype=TDT[dt])
+    w[:nw] = read(d.w, nw, dt)
+    w = w.double().reshape(16, d.w_rows, d.x.c)[:, :d.y.c]
     bias = read(d.bias, d.y.c).double() if d.bias else None
     y0 = View(d.y, ydt)
     pre = {}
@@ -936,6 +956,97 @@ def plan_of(call):
     if n == 'gan_bn_fold_multi':
         return f"{a[1]} entries, {a[2]} tiles"
     return ''
+
+
+# ---- plan classes, thin operands, required calls, padding channels (the RGB audit) -------------------------------------------------
+THIN_C = 8                   # an operand of at most this many channels: one 16-byte pixel (thin.hip, the tap-folded wgrad forms)
+
+
+def conv_class(d, op, requested=None):
+    """Plan class of a convolution descriptor as tests/test_cpu_launch_audit.py::plan_classes keys it: (op, tile, split or not,
+    parity form, statistics, tap sharing), and for the streaming kernels (tile rows 0) the sub-form - 'two-launch' (Z through the
+    workspace: conv_thin_n_kernel + conv_thin_col2im_kernel) or 'one-kernel' - from gan_conv_workspace_bytes.
+    requested: whether statistics groups were asked for (the host tables know; default: what the descriptor holds)."""
+    info, ts = conv_plan(d, op)
+    asked = bool(d.stats_groups) if requested is None else bool(requested)
+    st = ('full' if info[4] == -1 else 'stats' if info[4] > 0 else 'none') if asked else '-'
+    key = ('conv', op, info[0], info[1], info[2] > 1, info[3], st, ts)
+    if info[0] == 0:
+        key += ('two-launch' if L.load().gan_conv_workspace_bytes(C.byref(d), op) > 0 else 'one-kernel',)
+    return key
+
+
+def wgrad_class(d, wire=0):
+    info = (C.c_int32 * 4)()
+    L.check(L.load().gan_wgrad_plan_info(C.byref(d), info), "wgrad_plan_info")
+    return ('wgrad', info[0], info[1], info[2] > 1, info[3], int(wire))
+
+
+def same_class(key):
+    """A class key with a statistics request that was not honoured ('none') folded onto no request ('-'): nets._Builder drops such a
+    request from the descriptor it records, the host tables keep it."""
+    return tuple('-' if k == 'none' else k for k in key)
+
+
+def call_class(call):
+    """same_class() of a recorded conv / wgrad call (None for every other entry point)."""
+    if call.name in OPS:
+        return same_class(conv_class(call.args[0]._obj, OPS[call.name]))
+    if call.name == 'gan_conv_wgrad':
+        d = call.args[0]._obj
+        return wgrad_class(d, bool(d.dw_wire))
+    return None
+
+
+def thin_call(call):
+    """Does the call have an operand of <= THIN_C channels?  These are the calls whose code path depends on the image's channel
+    count: conv ops by x.c, y.c or w_rows, wgrad by big_c or small_c, gan_bias_grad / gan_act_bwd by the tensor they reduce / write."""
+    n, a = call.name, call.args
+    if n in OPS:
+        d = a[0]._obj
+        return d.x.c <= THIN_C or d.y.c <= THIN_C or d.w_rows <= THIN_C
+    if n == 'gan_conv_wgrad':
+        d = a[0]._obj
+        return d.big_c <= THIN_C or d.small_c <= THIN_C
+    if n == 'gan_bias_grad':
+        return a[1]._obj.c <= THIN_C
+    if n == 'gan_act_bwd':
+        return a[0]._obj.dy.c <= THIN_C
+    return False
+
+
+def missing_required(calls, rows, required):
+    """required: [(title, entry point, substring of the label, least number of distinct checked calls)].  A call counts when its
+    row was checked (res not None); distinct = different input tensors (x / big / dy pointer), so the two invocations of D count
+    twice and a repeated issue of one call once.  Returns the titles not met, with what was found."""
+    bad = []
+    for title, entry, frag, least in required:
+        seen = set()
+        for c, r in zip(calls, rows):
+            if c.name == entry and frag in c.label and r[4] is not None:
+                o = getattr(c.args[0], '_obj', None)
+                if isinstance(o, L.GanConvDesc):
+                    seen.add((o.x.ptr, o.y.ptr))
+                elif isinstance(o, L.GanWgradDesc):
+                    seen.add((o.big.ptr, o.small.ptr))
+                else:
+                    seen.add(id(c))
+        if len(seen) < least:
+            bad.append(f"{title}: {len(seen)} checked {entry} call(s) labelled '{frag}', {least} required")
+    return bad
+
+
+def pad_channels(named):
+    """named: [(name, NHWC device tensor of 8-channel pixels, real channels)] -> the names whose padding channels [real, 8) hold a
+    bit that is not zero (-0.0 included): thin-K reads whole 16-byte pixels, so such an element reaches the next layer."""
+    bad = []
+    for name, t, real in named:
+        assert t.shape[-1] == 8 and 0 < real <= 8, (name, tuple(t.shape), real)
+        pad = _bits(t[..., real:])
+        k = int((pad != 0).sum())
+        if k:
+            bad.append(f"{name}: {k} non-zero elements in channels [{real}, 8)")
+    return bad
 
 
 # ---- data-parallel step: an exchange that does nothing, the wire buffers, the update of whole networks ---------------------------

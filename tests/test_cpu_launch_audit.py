@@ -10,7 +10,12 @@
   - the gate of check_conv and the bit-equality of check_fold must be able to fail: a float32 model of convolution + bias +
     activation + rounding to storage sits inside the gate, the wrong variants a kernel could plausibly compute (a bias from the
     neighbouring channel / channel group / parity column, dropped on the second half of the columns, activation before the bias,
-    the wrong activation or slope; in the fold eps outside the root, an unscaled moving mean, the other layout) land >= 2x outside."""
+    the wrong activation or slope; in the fold eps outside the root, an unscaled moving mean, the other layout) land >= 2x outside;
+  - the RGB steps (channels = 3, tests/test_gpu_rgb_audit.py): the tables take a `channels` parameter, the class of a streaming
+    launch carries its sub-form (one kernel, or Z through the workspace in two launches), RGB_AUDITED must reach every class with a
+    thin operand, and a float32 model of the two-launch thin-N convolution sits inside the gate while its wrong variants (swapped
+    taps, the other parity's tap table at the border, a neighbouring channel's Z or bias, a dropped channel, a 3-pitch store, the
+    wrong weight rows, dw rows at stride 8) do not."""
 import ctypes as C
 import math
 import os
@@ -76,19 +81,25 @@ def test_audit_ulp_gate():
 # ---- plan coverage ---------------------------------------------------------------------------------------------------------
 # The step objects need a device to be built, so the launches are listed here, one table per network, with the shapes, channel
 # counts, request flags (fused statistics, GanBwdFuse with its cols / skip input, GanNormFuse, bias / activation / fp32 logits) and
-# wgrad scheduling hints that gan_amd/nets.py and gan_amd/steps.py give them in the captured one-GPU step at channels = 1 (the steps
-# the GPU audit builds).
+# wgrad scheduling hints that gan_amd/nets.py and gan_amd/steps.py give them in the captured one-GPU step at `channels` image channels
+# (1: the steps the GPU audit builds; 3: those of tests/test_gpu_rgb_audit.py).
 G_DOWN = [64, 128, 256, 512, 512, 512, 512, 512]
 G_UP = [512, 512, 512, 512, 256, 128, 64]
-CH = 1
 
 
 def T(n, h, c):
     return L.GanTensor(16, n, h, h, c, c)
 
 
-def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None):
-    """{class: label} of every conv / wgrad launch of one captured step.
+def IMG(n, h, c):
+    """c real channels of an 8-channel image-side pixel (out, dxin, dgen2: the views nets.py makes with Buf.view(0, c))."""
+    return L.GanTensor(16, n, h, h, c, 8)
+
+
+def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None, channels=1, thin=None):
+    """{class: label} of every conv / wgrad launch of one captured step at `channels` image channels (1: the steps of
+    tests/test_gpu_launch_audit.py; 3: tests/test_gpu_rgb_audit.py).  thin: a set that receives the classes of the launches with an
+    operand of <= 8 channels (launch_audit.THIN_C: the launches whose code path depends on `channels`).
     ddp: None - the one-GPU step; 'direct' - the data-parallel Pix2Pix step on its bucketed schedule with the bf16 wire
     (Pix2PixStep._capture_bucketed): every wgrad launch is given its place in the wire buffer and writes it where
     gan_wgrad_wire_direct says it can; 'plain' - every other data-parallel schedule (fp32 wire, ddp_wire_direct = False, the phased
@@ -124,9 +135,10 @@ def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None):
                           16 if groups else None, groups, 1 << 30, C.addressof(bf) if bf is not None else None,
                           C.addressof(nf) if nf is not None else None)
         assert lib.gan_conv_plan_info(C.byref(d), op, info) == 0, tag
-        ts = lib.gan_conv_tap_shared(C.byref(d), op)
-        st = ('full' if info[4] == -1 else 'stats' if info[4] > 0 else 'none') if groups else '-'
-        out.setdefault(('conv', op, info[0], info[1], info[2] > 1, info[3], st, ts), tag)
+        key = A.conv_class(d, op, requested=groups)      # (streaming kernels: + the one-kernel / two-launch sub-form)
+        out.setdefault(key, tag)
+        if thin is not None and min(x.c, y.c, d.w_rows) <= A.THIN_C:
+            thin.add(key)
 
     def wgrad(tag, big, small, big_c, small_c, stride, conc):
         d = L.GanWgradDesc(dt, stride, big, small, 16, big_c, small_c, 0, 16, 1 << 40, conc, None, 64 if ddp == 'direct' else None)
@@ -137,7 +149,11 @@ def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None):
             if not wire:
                 d.dw_wire = None                     # (as nets._Builder.wgrad does)
         assert lib.gan_wgrad_plan_info(C.byref(d), winfo) == 0, tag
-        out.setdefault(('wgrad', winfo[0], winfo[1], winfo[2] > 1, winfo[3], wire), tag)
+        key = ('wgrad', winfo[0], winfo[1], winfo[2] > 1, winfo[3], wire)
+        assert key == A.wgrad_class(d, wire)
+        out.setdefault(key, tag)
+        if thin is not None and min(big_c, small_c) <= A.THIN_C:
+            thin.add(key)
         if strings is not None:
             strings.add(A.wgrad_plan(d))
 
@@ -157,29 +173,29 @@ def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None):
                 conv(f"G.down{i} dgrad", 1, T(n, hs[i], co), T(n, h_in, below), groups=g, norm_fuse=i > 1, bwd=(below, i > 1, True))
             cin = co
         if need_dx:
-            conv("G.down0 dx dgrad", 1, T(n, hs[0], 64), T(n, S, CH))
+            conv("G.down0 dx dgrad", 1, T(n, hs[0], 64), IMG(n, S, channels))
         for j, co in enumerate(G_UP):
             h_in = hs[7 - j]
             conv(f"G.up{j} fwd", 2, T(n, h_in, cin_up[j]), T(n, 2 * h_in, co), groups=g, norm_fuse=True)
             cols = G_UP[j - 1] if j > 0 else 512
             conv(f"G.up{j} dgrad", 3, T(n, 2 * h_in, co), T(n, h_in, cin_up[j]), groups=g, norm_fuse=True, bwd=(cols, True, False))
-        conv("G.last fwd", 2, T(n, hs[0], 128), T(n, S, CH), act=L.ACT_TANH, bias=True)
+        conv("G.last fwd", 2, T(n, hs[0], 128), IMG(n, S, channels), act=L.ACT_TANH, bias=True)
         conv("G.last dgrad", 3, T(n, S, 8), T(n, hs[0], 128), groups=g, bwd=(G_UP[6], True, False))
 
     def generator_wgrads(n, conc):
         cin = 8
         for i, co in enumerate(G_DOWN):
-            big_c = CH if i == 0 else G_DOWN[i - 1]
+            big_c = channels if i == 0 else G_DOWN[i - 1]
             wgrad(f"G.down{i} wgrad", T(n, S >> i, cin), T(n, hs[i], co), big_c, co, 2, conc)
             cin = co
         for j, co in enumerate(G_UP):
             h_in = hs[7 - j]
             wgrad(f"G.up{j} wgrad", T(n, 2 * h_in, co), T(n, h_in, cin_up[j]), co, cin_up[j], 2, conc)
-        wgrad("G.last wgrad", T(n, S, 8), T(n, hs[0], 128), CH, 128, 2, conc)
+        wgrad("G.last wgrad", T(n, S, 8), T(n, hs[0], 128), channels, 128, 2, conc)
 
     s1, s2, s3 = S // 2, S // 4, S // 8
     s4, s5 = s3 - 1, s3 - 2
-    d_cin = 2 * CH if model == 'pix2pix' else CH
+    d_cin = 2 * channels if model == 'pix2pix' else channels
     layers = [('down1', 64, 128, s1, s2, 2), ('down2', 128, 256, s2, s3, 2), ('conv', 256, 512, s3, s4, 1)]
 
     def disc_forward(n, calls):
@@ -201,7 +217,7 @@ def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None):
                 wgrad(f"D.{name} wgrad", T(n, hi, ci), T(n, ho, co), ci, co, st, conc)
             wgrad("D.down0 wgrad", T(n, S, 8), T(n, s1, 64), d_cin, 64, 2, conc)
         else:
-            conv("D.down0 dx dgrad", 1, T(n, s1, 64), T(n, S, CH), w_rows=d_cin)
+            conv("D.down0 dx dgrad", 1, T(n, s1, 64), IMG(n, S, channels), w_rows=d_cin)
 
     if model == 'pix2pix':
         generator(B, False)
@@ -248,10 +264,11 @@ EVAL_SWEEP = {('generator', 256): range(1, 65), ('generator', 512): range(1, 17)
               ('discriminator', 256): range(1, 65), ('discriminator', 512): range(1, 17)}
 
 
-def eval_launches(net, B, S, dt=L.BF16):
-    """[(tag, op, plan info, tap-shared, bias present, activation)] of the convolution launches of one eval forward, with the
-    views (channel slices of the concat buffers, their real pitches), bias and activation that nets.GenEvalCall / nets.DiscEvalCall
-    give them at channels = 1: no statistics, no fused epilogue requests."""
+def eval_launches(net, B, S, dt=L.BF16, channels=1):
+    """[(tag, op, plan info, tap-shared, bias present, activation, sub-form)] of the convolution launches of one eval forward, with
+    the views (channel slices of the concat buffers, their real pitches), bias and activation that nets.GenEvalCall /
+    nets.DiscEvalCall give them at `channels` image channels: no statistics, no fused epilogue requests.  sub-form: () for the tiled
+    GEMM, ('one-kernel',) or ('two-launch',) for the streaming kernels (launch_audit.conv_class)."""
     lib = L.load()
     out = []
 
@@ -262,7 +279,7 @@ def eval_launches(net, B, S, dt=L.BF16):
         d = L.GanConvDesc(dt, stride, x, y, 16, y.c, 16 if bias else None, act, 0.3, y_f32, 16, 1 << 40, None, 0, 0, None, None)
         info = (C.c_int32 * 5)()
         assert lib.gan_conv_plan_info(C.byref(d), op, info) == 0, tag
-        out.append((tag, op, list(info), lib.gan_conv_tap_shared(C.byref(d), op), bool(bias), act))
+        out.append((tag, op, list(info), lib.gan_conv_tap_shared(C.byref(d), op), bool(bias), act, A.conv_class(d, op)[8:]))
 
     if net == 'generator':
         hs = [S >> (i + 1) for i in range(8)]
@@ -276,7 +293,7 @@ def eval_launches(net, B, S, dt=L.BF16):
         for j in range(7):
             x = V(B, hs[7], 512) if j == 0 else V(B, hs[7 - j], pitch[j - 1])
             conv(f"G.up{j}", 2, x, V(B, hs[6 - j], G_UP[j], pitch[j]), act=L.ACT_RELU)
-        conv("G.last", 2, V(B, hs[0], pitch[6]), V(B, S, CH, 8), act=L.ACT_TANH)
+        conv("G.last", 2, V(B, hs[0], pitch[6]), V(B, S, channels, 8), act=L.ACT_TANH)
     else:
         s1, s2, s3 = S // 2, S // 4, S // 8
         s4, s5 = s3 - 1, s3 - 2
@@ -288,18 +305,18 @@ def eval_launches(net, B, S, dt=L.BF16):
     return out
 
 
-def eval_plan_classes(net, B, S, dt=L.BF16):
+def eval_plan_classes(net, B, S, dt=L.BF16, channels=1):
     """{class: tag}: the class key of plan_classes (op, tile, split or not, parity form, statistics, tap sharing) plus (bias
-    present, activation)."""
-    return {('conv', op, info[0], info[1], info[2] > 1, info[3], '-', ts, bias, act): tag
-            for tag, op, info, ts, bias, act in reversed(eval_launches(net, B, S, dt))}
+    present, activation) and, for the streaming kernels, their sub-form."""
+    return {('conv', op, info[0], info[1], info[2] > 1, info[3], '-', ts, bias, act) + sub: tag
+            for tag, op, info, ts, bias, act, sub in reversed(eval_launches(net, B, S, dt, channels))}
 
 
-def eval_plan_strings(net, B, S, dt=L.BF16):
+def eval_plan_strings(net, B, S, dt=L.BF16, channels=1):
     """The launches as tests/test_gpu_eval_audit.py names what it recorded: check_conv's plan string + bias + activation.  The GPU
     test fails if the set it saw differs from this one, so a change in nets.py cannot leave the table above behind."""
     return {f"op{op} tile {info[0]}x{info[1]} split {info[2]} par {info[3]} stats {info[4]} ts {ts} bias {int(bias)} act {act}"
-            for tag, op, info, ts, bias, act in eval_launches(net, B, S, dt)}
+            for tag, op, info, ts, bias, act, sub in eval_launches(net, B, S, dt, channels)}
 
 
 def eval_missing(audited):
@@ -678,3 +695,224 @@ def test_ddp_gates_pass_the_float32_model_and_reject_wrong_variants():
     # gan_grad_pack, the bit equality of check_pack_range) sees it
     t = _ddp_model('truncation instead of RNE')
     assert t['wire'] <= 1.0 and t['wire rounding bias'] >= 2.0
+
+
+# ---- RGB steps (channels = 3): plan coverage --------------------------------------------------------------------------------------
+# tests/test_gpu_rgb_audit.py's cases: (model, size) -> batches of the one-GPU training steps, (network, size) -> batches of the eval
+# forwards.  At channels = 3 the image-side launches leave the one-kernel thin-N form (thin.hip: y.c <= 2) for conv_thin_n_kernel +
+# conv_thin_col2im_kernel; the sweep below (the one of SWEEP: B = 1..16 at 256x256, 1..8 at 512x512) asks which batches the classes
+# WITH A THIN OPERAND need - every other class is one the channels = 1 audit covers at the same batch (asserted below).
+RGB = 3
+RGB_AUDITED = {('pix2pix', 256): (1, 9), ('pix2pix', 512): (1,), ('cyclegan', 256): (1,)}
+RGB_SWEEP = SWEEP
+RGB_EVAL_AUDITED = {('generator', 256): (1, 9), ('discriminator', 256): (1, 9)}
+RGB_EVAL_SWEEP = {('generator', 256): range(1, 17), ('discriminator', 256): range(1, 17)}
+
+
+def rgb_thin_classes(model, B, S):
+    thin = set()
+    plan_classes(model, B, S, channels=RGB, thin=thin)
+    return thin
+
+
+def rgb_missing(audited):
+    missing = []
+    for key, batches in RGB_SWEEP.items():
+        model, S = key
+        reach = {}
+        for B in batches:
+            for cls in rgb_thin_classes(model, B, S):
+                reach.setdefault(cls, []).append(B)
+        seen = set()
+        for B in audited[key]:
+            seen |= rgb_thin_classes(model, B, S)
+        for cls, where in reach.items():
+            if cls not in seen:
+                missing.append(f"{model} {S}x{S} channels 3: thin class {cls} reached at B = {where}, audited {audited[key]}")
+    return missing
+
+
+@pytest.mark.skipif(not HAVE_LIB, reason="library not built")
+def test_rgb_audited_batches_reach_every_thin_plan_class():
+    missing = rgb_missing(RGB_AUDITED)
+    assert not missing, "thin plan classes at channels = 3 that no RGB case reaches:\n" + "\n".join(missing)
+    for key, sweep in RGB_SWEEP.items():
+        model, S = key
+        for B in sweep:
+            thin3, thin1 = set(), set()
+            c3 = plan_classes(model, B, S, channels=RGB, thin=thin3)
+            c1 = plan_classes(model, B, S, thin=thin1)
+            # the launches without a thin operand do not know the image's channel count: same classes as at channels = 1
+            assert set(c3) - thin3 == set(c1) - thin1, (key, B)
+            # every thin-N launch at channels = 1 is the one-kernel form (no existing class splits); at 3 the image-side ones are not
+            assert not any(k[-1] == 'two-launch' for k in c1), (key, B)
+            # (a class carries the tag of its first launch: CycleGAN's G.down0 dx dgrad and D.down0 dx dgrad are one class)
+            two = {(k[1], c3[k]) for k in c3 if k[-1] == 'two-launch'}
+            assert two == {(2, "G.last fwd"), (1, "G.down0 dx dgrad" if model == 'cyclegan' else "D.down0 dx dgrad")}, (key, B, two)
+    # the eval forwards: the head is the only launch that changes (two-launch form with bias + tanh)
+    for key, sweep in RGB_EVAL_SWEEP.items():
+        net, S = key
+        reach = {}
+        for B in sweep:
+            for cls, tag in eval_plan_classes(net, B, S, channels=RGB).items():
+                if cls[2] == 0:
+                    reach.setdefault(cls, []).append(B)
+        seen = set()
+        for B in RGB_EVAL_AUDITED[key]:
+            seen |= set(eval_plan_classes(net, B, S, channels=RGB))
+        gone = {cls: bs for cls, bs in reach.items() if cls not in seen}
+        assert not gone, f"eval {net} channels 3: streaming-kernel classes {gone} not reached by {RGB_EVAL_AUDITED[key]}"
+    assert any(k[-1] == 'two-launch' and k[8:10] == (True, L.ACT_TANH) for k in eval_plan_classes('generator', 1, 256, channels=RGB))
+    # the test can fail: a case list without a model's batches names them
+    less = rgb_missing({**RGB_AUDITED, ('cyclegan', 256): ()})
+    assert less and all('cyclegan 256x256' in m for m in less)
+
+
+def test_thin_n_grid_cap_is_first_exceeded_at_batch_9():
+    """conv_thin_n_kernel: tiles of 16 pixels, 4 per workgroup, grid capped at 2,048 workgroups (thin.hip, thin_launch).  The head
+    reads 128 x 128 pixels per image at 256 x 256: tiles = 1024 B, workgroups 256 B > 2048 iff B > 8.  At B = 9 the second grid-stride
+    trip is ragged: 9,216 tiles over 8,192 waves."""
+    def groups(B, h):
+        return (B * h * h + 15) // 16 // 4
+    assert [B for B in range(1, 17) if groups(B, 128) > 2048][0] == 9
+    assert groups(9, 128) * 4 - 2048 * 4 == 1024                     # 1,024 of 8,192 waves take a second tile
+    assert groups(1, 256) == 1024                                    # 512 x 512, B = 1: within one trip
+    assert 9 in RGB_AUDITED[('pix2pix', 256)] and 9 in RGB_EVAL_AUDITED[('generator', 256)]
+
+
+# ---- the RGB gates must be able to fail -----------------------------------------------------------------------------------------
+# A numpy float32 model of the two-launch thin-N convolution (thin.hip): Z[pixel][c][tap] = x[pixel, :] . W[tap][c][:] in fp32, then
+# per output pixel the col2im gather of the valid taps (the parity table y[2g + p] = sum_a x[g + p - a] w[1 - p + 2a], or the stride
+# table y[g] = sum_a x[g S - 1 + a] w[a]), bias, activation and ONE rounding, stored at channel c of the view's 8-channel pixel.
+# Smallest shape with all four borders and both parities: 1 x 8 x 8 source pixels, 64 -> 3 channels.
+RGB_CO, RGB_CI, RGB_H = 3, 64, 8
+RGB_CONV_VARIANTS = ['ky / kx swapped', 'tap table of the other parity on the last row / column', 'channel c gathers Z of c + 1',
+                     'bias rotated by one channel', 'last real channel dropped', 'stored at c of a 3-pitch',
+                     'weight rows [0, 3) for [3, 6)']
+SENT = {L.BF16: 0x7FA5, L.F16: 0x7E55}        # NaN patterns no kernel produces: what the pad channels / unwritten outputs would keep
+
+
+def _rgb_case(dt, seed, rows=RGB_CO):
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randint(0, 256, (1, RGB_H, RGB_H, RGB_CI), generator=g).float() / 127.5 - 1.0).to(ROUND[dt]).double()
+    w = (0.03 * torch.randn((16, rows, RGB_CI), generator=g)).to(ROUND[dt]).double()
+    bias = (0.2 * torch.randn(RGB_CO, generator=g) + 0.1).float().double()
+    return x, w, bias
+
+
+def _thin_n_model(x, w, bias, parity, act, dt, variant=None, row0=0):
+    """-> raw int16 span of the [1, Ho, Wo] x 8-channel output buffer (pad channels and unwritten elements keep SENT).
+    w: [16][w_rows][64], the launch reads rows [row0, row0 + 3) (D's dx dgrad: the pointer advanced by row0 rows)."""
+    f = np.float32
+    if variant == 'weight rows [0, 3) for [3, 6)':
+        row0 = 0
+    xs = x.numpy().astype(f).reshape(RGB_H * RGB_H, RGB_CI)
+    ws = w.numpy().astype(f)[:, row0:row0 + RGB_CO]                           # [tap][c][ci]
+    Z = np.einsum('pi,tci->pct', xs, ws).astype(f).reshape(RGB_H, RGB_H, RGB_CO, 16)
+    Ho = 2 * RGB_H if parity else RGB_H - 1
+    b = bias.numpy().astype(f)
+    if variant == 'bias rotated by one channel':
+        b = np.roll(b, 1)
+    pitch = 3 if variant == 'stored at c of a 3-pitch' else 8
+    raw = np.full(Ho * Ho * 8, SENT[dt], dtype=np.uint16)
+    nco = RGB_CO - 1 if variant == 'last real channel dropped' else RGB_CO
+    for Y in range(Ho):
+        for X in range(Ho):
+            if parity:
+                py, gy, px, gx = Y & 1, Y >> 1, X & 1, X >> 1
+                if variant == 'tap table of the other parity on the last row / column':
+                    py, px = (py ^ 1 if Y == Ho - 1 else py), (px ^ 1 if X == Ho - 1 else px)
+                ty = [(gy + py - a, 1 - py + 2 * a) for a in range(2)]
+                tx = [(gx + px - a, 1 - px + 2 * a) for a in range(2)]
+            else:
+                ty = [(Y - 1 + a, a) for a in range(4)]
+                tx = [(X - 1 + a, a) for a in range(4)]
+            acc = np.zeros(RGB_CO, dtype=f)
+            for iy, ky in ty:
+                if not 0 <= iy < RGB_H:
+                    continue
+                for ix, kx in tx:
+                    if not 0 <= ix < RGB_H:
+                        continue
+                    tap = kx * 4 + ky if variant == 'ky / kx swapped' else ky * 4 + kx
+                    z = Z[iy, ix, :, tap]
+                    acc = (acc + (np.roll(z, -1) if variant == 'channel c gathers Z of c + 1' else z)).astype(f)
+            v = torch.from_numpy((acc + b).astype(f))
+            v = A.act_f(v, act, 0.3).to(ROUND[dt]).view(torch.int16).numpy().view(np.uint16)
+            o = (Y * Ho + X) * pitch
+            raw[o:o + nco] = v[:nco]
+    return torch.from_numpy(raw.view(np.int16).copy()), Ho
+
+
+def _thin_n_ratios(op, stride, act, dt, use_bias, variant=None, row0=0):
+    """The model's output through check_conv's own items: 'y' (y_gate of conv_pre) and 'y untouched outside y.c'."""
+    x, w, bias = _rgb_case(dt, 40 + op + stride, rows=RGB_CO + row0)
+    parity = stride == 2
+    raw, Ho = _thin_n_model(x, w, bias if use_bias else torch.zeros(RGB_CO).double(), parity, act, dt, variant, row0)
+    t = L.GanTensor(16, 1, Ho, Ho, RGB_CO, 8)
+    span = (Ho * Ho - 1) * 8 + RGB_CO
+    y0 = A.View.of_host(torch.full((span,), SENT[dt], dtype=torch.int16).view(ROUND[dt]), t, dt)
+    y1 = A.View.of_host(raw[:span].view(ROUND[dt]), t, dt)
+    ref, eacc = A.conv_pre(op, x, w[:, row0:row0 + RGB_CO], bias if use_bias else None, stride)
+    assert tuple(ref.shape) == (1, Ho, Ho, RGB_CO)
+    out, gate = A.y_gate(ref, eacc, act, 0.3, dt)
+    return {'y': A.ratio(y1.dense(), out, gate), 'y untouched outside y.c': A.untouched(y0, y1, 0, RGB_CO)}
+
+
+def _thin_wgrad_ratios(dt, big_c, variant=None):
+    """float32 model of a wgrad launch with a thin big side (G.down0 / G.last: 3 of 8 channels, D.down0: 6 of 8): dw[tap][big_c][64]
+    through check_wgrad's plain-write item."""
+    g = torch.Generator().manual_seed(50 + big_c)
+    big = torch.zeros((1, 16, 16, 8))
+    big[..., :big_c] = torch.randint(0, 256, (1, 16, 16, big_c), generator=g).float() / 127.5 - 1.0
+    big = big.to(ROUND[dt])
+    small = (0.05 * torch.randn((1, 8, 8, 64), generator=g)).to(ROUND[dt])
+    dw = (F_unfold(big[..., :big_c].float()).t() @ small.float().reshape(-1, 64)).reshape(16, big_c, 64)
+    got = torch.zeros(16 * big_c * 64)
+    if variant == 'dw rows written with row stride 8':
+        rows = (torch.arange(16)[:, None] * 8 + torch.arange(big_c)[None, :]).reshape(-1)
+        keep = rows < 16 * big_c                                            # (a kernel would write the rest behind the tensor)
+        got.view(16 * big_c, 64)[rows[keep]] = dw.reshape(-1, 64)[keep]
+    else:
+        got.copy_(dw.reshape(-1))
+    ref = A.wgrad_ref(big.double(), small.double(), 2, big_c, 64).reshape(-1)
+    eg = A.wgrad_acc_bound(big.double(), small.double(), big_c, 64)
+    return {'dw': A.ratio(got, ref, eg + A.ulp(ref, L.F32))}
+
+
+# (entry point, stride, activation, bias, first weight row): the head, a stride-1 / pad-1 layer of 3 outputs, D's dx dgrad
+RGB_FORMS = {'convT_fwd parity + bias + tanh (G.last)': (2, 2, L.ACT_TANH, True, 0),
+             'conv_fwd stride 1 pad 1 + bias': (0, 1, L.ACT_NONE, True, 0),
+             'conv_dgrad parity, rows [3, 6) of 6 (D.down0 dx dgrad)': (1, 2, L.ACT_NONE, False, 3)}
+
+
+@pytest.mark.parametrize('dt', [L.BF16, L.F16], ids=['bf16', 'f16'])
+def test_rgb_gates_pass_the_float32_model_and_reject_wrong_variants(dt):
+    smallest = {}
+    for form, (op, stride, act, use_bias, row0) in RGB_FORMS.items():
+        good = _thin_n_ratios(op, stride, act, dt, use_bias, None, row0)
+        print(f"{form}, dtype {dt}: float32 model worst error / gate " + ', '.join(f"{k} {v:.3f}" for k, v in good.items()))
+        assert all(v <= 0.5 for v in good.values()), (form, good)
+        for v in RGB_CONV_VARIANTS:
+            if v == 'tap table of the other parity on the last row / column' and stride != 2:
+                continue                          # (the stride form has one tap table)
+            if v == 'bias rotated by one channel' and not use_bias:
+                continue
+            if v == 'weight rows [0, 3) for [3, 6)' and not row0:
+                continue
+            r = _thin_n_ratios(op, stride, act, dt, use_bias, v, row0)
+            out = {k: x for k, x in r.items() if x >= 2.0}
+            print(f"  {v}: " + (', '.join(f"{k} {x:.1f}" for k, x in out.items()) or f"NOT SEEN ({r})"))
+            assert out, (form, v, r)
+            smallest[v] = min(smallest.get(v, math.inf), max(out.values()))
+            if v == 'stored at c of a 3-pitch':
+                assert r['y untouched outside y.c'] == math.inf
+    assert set(smallest) == set(RGB_CONV_VARIANTS)
+    for big_c in (3, 6):
+        good = _thin_wgrad_ratios(dt, big_c)
+        bad = _thin_wgrad_ratios(dt, big_c, 'dw rows written with row stride 8')
+        print(f"wgrad big_c {big_c}, dtype {dt}: float32 model dw {good['dw']:.3f}; dw rows written with row stride 8: {bad['dw']:.1f}")
+        assert good['dw'] <= 0.5 and bad['dw'] >= 2.0
+        smallest['dw rows written with row stride 8'] = min(smallest.get('dw rows written with row stride 8', math.inf), bad['dw'])
+    worst = min(smallest, key=smallest.get)
+    print(f"smallest ratio of a wrong variant: {smallest[worst]:.1f} ({worst})")

@@ -2,8 +2,10 @@
 its own against an fp64 reference of the values it read (tests/launch_audit.py): per-element gates near one output ulp instead of
 the step-level cosine / agreement gates of test_gpu_golden_full.py, and every kernel / fusion the planner picks for these batch
 sizes - the partial batches of an epoch included (gan_amd/data.py keeps the last one; Pix2Pix._step_for captures a step per batch
-size) - is reached.  AUDIT_CASES is the batch list; tests/test_cpu_launch_audit.py asserts on the host planners alone that it
-reaches every plan class of B = 1..16 at 256x256 and B = 1..8 at 512x512."""
+size) - is reached, for steps built at channels = 1.  AUDIT_CASES is the batch list; tests/test_cpu_launch_audit.py asserts on the
+host planners alone that it reaches every plan class of B = 1..16 at 256x256 and B = 1..8 at 512x512.  At channels = 3 the
+image-side layers leave the one-kernel thin-N form for conv_thin_n_kernel + conv_thin_col2im_kernel, which no case here launches:
+tests/test_gpu_rgb_audit.py audits the launches that depend on the channel count."""
 import gc
 import time
 
