@@ -13,6 +13,8 @@ activation are written by their producers straight into channel slices of one NH
 from __future__ import annotations
 
 import ctypes as C
+from types import MappingProxyType
+from typing import Any, Callable, Mapping, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -32,6 +34,46 @@ STATS_RESERVE = 8 << 20      # room kept behind a conv's split-K slabs for its f
 
 def pad8(c):
     return (c + 7) // 8 * 8
+
+
+class Op(NamedTuple):
+    """One pre-filled C call of an op list: `fn(*args, stream)`, its label for error messages, what the planner said about the launch
+    (`meta`: empty for ops that have nothing to tell, never None) and whether it is a side-stream op (it only feeds Adam, so a staged
+    backward runs it on a wgrad lane).  Always five long; positional access (op[0](*op[1], st), op[2], op[3].get) keeps working."""
+    fn: Callable
+    args: tuple
+    label: str
+    meta: Mapping[str, Any] = MappingProxyType({})
+    side: bool = False
+
+
+class ConvPlan(NamedTuple):
+    """What the plan answered for one convolution descriptor (_Builder.conv)."""
+    full: bool            # GanNormFuse honoured: the launch finishes the layer (no norm ops follow)
+    stats_chunks: int     # > 0: the launch writes normalisation-statistics partials, this many chunks (0: not fusable for this shape)
+    bwd_fused: int        # > 0: a dgrad launch carries the GanBwdFuse epilogue; the chunk count for gan_norm_act_bwd_fused
+    partial_ptr: int      # where the partials live: behind the launch's own scratch (split-K slabs) in the lane workspace
+
+
+class BwdKey(NamedTuple):
+    """The arguments of one backward build (GenCall._build_bwd): the key of its plan."""
+    use_dgen2: bool = False
+    need_dx: bool = False
+    accumulate: bool = False
+    wgrads: str = 'own'
+    adam: Optional[tuple] = None
+    wire: Optional[int] = None
+
+
+class BwdPlan(list):
+    """What one backward build produced: the op list itself - Ctx.run and every other reader of op lists take the plan as it is -
+    and, with it, what the build decided."""
+
+    def __init__(self, ops, adam_fused=(), wire_direct=(), dy0_in_dA=None):
+        super().__init__(ops)
+        self.adam_fused = tuple(adam_fused)      # kernels whose wgrad launch carries Adam (GanAdamFuse)
+        self.wire_direct = tuple(wire_direct)    # kernels whose wgrad launch writes the wire format (GanWgradDesc.dw_wire)
+        self.dy0_in_dA = dy0_in_dA               # generator: down0's output gradient lives in dA[0] (host and guest must agree)
 
 
 def workspace_mb_for(batch, size, channels=1, calls=2):
@@ -274,7 +316,7 @@ class ParamSet:
                 self.tr[name] = torch.zeros((16, B, pad8(A)), dtype=ctx.tdtype, device=dev)
         # one launch refreshes every NK copy of the network (device table of GanPrepEntry)
         self._prep_table, self._prep_args = self._kernel_table(list(self.nat))
-        self._prep_ops = [(ctx.lib.gan_weights_prepare_multi, self._prep_args, "weights_prepare_multi")]
+        self._prep_ops = [Op(ctx.lib.gan_weights_prepare_multi, self._prep_args, "weights_prepare_multi")]
         self._segments = None
 
     def _kernel_table(self, names):
@@ -301,7 +343,7 @@ class ParamSet:
         self._segments = cache[cut_names]
 
     def adam_begin_ops(self, lr, b1, b2):
-        return [(self.ctx.lib.gan_adam_begin, (self.step.data_ptr(), self.lr_t.data_ptr(), lr, b1, b2, self.ctx.ls_ptr), "adam_begin")]
+        return [Op(self.ctx.lib.gan_adam_begin, (self.step.data_ptr(), self.lr_t.data_ptr(), lr, b1, b2, self.ctx.ls_ptr), "adam_begin")]
 
     def adam_segment_ops(self, seg, b1, b2, eps=1e-7, grad_scale=1.0, vectors=False, kernels=True, wire_ptr=None):
         """Fused Adam + NK refresh of kernel segment `seg` (split_kernels_at), optionally followed by the vectors'
@@ -312,12 +354,12 @@ class ParamSet:
         ptrs = (self.master.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wire_ptr or self.grad.data_ptr())
         ops = []
         if kernels:
-            ops.append((lib.gan_adam_prepare_multi, self._segments[seg][1] + ptrs + (self.lr_t.data_ptr(), b1, b2, eps, grad_scale, self.ctx.ls_ptr, gw),
+            ops.append(Op(lib.gan_adam_prepare_multi, self._segments[seg][1] + ptrs + (self.lr_t.data_ptr(), b1, b2, eps, grad_scale, self.ctx.ls_ptr, gw),
                         "adam_prepare_multi"))
         nvec = self.total - self.vec_start
         if vectors and nvec > 0:
             vptrs = tuple(p_ + 4 * self.vec_start for p_ in ptrs[:3]) + (ptrs[3] + (2 if gw else 4) * self.vec_start,)
-            ops.append((lib.gan_adam_tf, vptrs + (nvec, self.lr_t.data_ptr(), b1, b2, eps, grad_scale, self.ctx.ls_ptr, gw), "adam_tf"))
+            ops.append(Op(lib.gan_adam_tf, vptrs + (nvec, self.lr_t.data_ptr(), b1, b2, eps, grad_scale, self.ctx.ls_ptr, gw), "adam_tf"))
         return ops
 
     def adam_fuse_desc(self, name, b1, b2, eps=1e-7):
@@ -339,11 +381,11 @@ class ParamSet:
         ptrs = (self.master.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.grad.data_ptr())
         ops = []
         if rest is not None:
-            ops.append((lib.gan_adam_prepare_multi, rest[1] + ptrs + (self.lr_t.data_ptr(), b1, b2, eps, 1.0, self.ctx.ls_ptr, 0), "adam_prepare_multi"))
+            ops.append(Op(lib.gan_adam_prepare_multi, rest[1] + ptrs + (self.lr_t.data_ptr(), b1, b2, eps, 1.0, self.ctx.ls_ptr, 0), "adam_prepare_multi"))
         nvec = self.total - self.vec_start
         if nvec > 0:
             vptrs = tuple(p_ + 4 * self.vec_start for p_ in ptrs)
-            ops.append((lib.gan_adam_tf, vptrs + (nvec, self.lr_t.data_ptr(), b1, b2, eps, 1.0, self.ctx.ls_ptr, 0), "adam_tf"))
+            ops.append(Op(lib.gan_adam_tf, vptrs + (nvec, self.lr_t.data_ptr(), b1, b2, eps, 1.0, self.ctx.ls_ptr, 0), "adam_tf"))
         return ops
 
     def ptr(self, name, which='master'):
@@ -355,7 +397,7 @@ class ParamSet:
 
     def grads_check_ops(self):
         """fp16 path: raise the loss-scale state's non-finite flag if this network's gradients hold an inf/nan."""
-        return [(self.ctx.lib.gan_grads_check, (self.grad.data_ptr(), self.total, self.ctx.ls_ptr), "grads_check")]
+        return [Op(self.ctx.lib.gan_grads_check, (self.grad.data_ptr(), self.total, self.ctx.ls_ptr), "grads_check")]
 
     def trainable_count(self):
         return int(sum(np.prod(s) for _, s in self.entries.values()))
@@ -386,13 +428,13 @@ class ParamSet:
         table_ptr, n_ents, tiles, dt = self._prep_args
         gw = 1 if wire_ptr else 0
         ptrs = (self.master.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wire_ptr or self.grad.data_ptr())
-        ops = [(lib.gan_adam_begin, (self.step.data_ptr(), self.lr_t.data_ptr(), lr, b1, b2, self.ctx.ls_ptr), "adam_begin"),
-               (lib.gan_adam_prepare_multi, (table_ptr, n_ents, tiles, dt) + ptrs + (self.lr_t.data_ptr(), b1, b2, eps, grad_scale, self.ctx.ls_ptr, gw),
+        ops = [Op(lib.gan_adam_begin, (self.step.data_ptr(), self.lr_t.data_ptr(), lr, b1, b2, self.ctx.ls_ptr), "adam_begin"),
+               Op(lib.gan_adam_prepare_multi, (table_ptr, n_ents, tiles, dt) + ptrs + (self.lr_t.data_ptr(), b1, b2, eps, grad_scale, self.ctx.ls_ptr, gw),
                 "adam_prepare_multi")]
         nvec = self.total - self.vec_start
         if nvec > 0:
             vptrs = tuple(p_ + 4 * self.vec_start for p_ in ptrs[:3]) + (ptrs[3] + (2 if gw else 4) * self.vec_start,)
-            ops.append((lib.gan_adam_tf, vptrs + (nvec, self.lr_t.data_ptr(), b1, b2, eps, grad_scale, self.ctx.ls_ptr, gw), "adam_tf"))
+            ops.append(Op(lib.gan_adam_tf, vptrs + (nvec, self.lr_t.data_ptr(), b1, b2, eps, grad_scale, self.ctx.ls_ptr, gw), "adam_tf"))
         if stream is not None:
             self.ctx.run_on(ops, stream)
         else:
@@ -455,7 +497,8 @@ def init_params_numpy(spec, seed):
 
 # --------------------------------------------------------------------------------------------------
 class _Builder:
-    """Helpers that turn layer descriptions into (fn, args, label) C calls."""
+    """Helpers that turn layer descriptions into Op records.  What the planner answered for a descriptor comes back with the op
+    (conv -> ConvPlan, wgrad -> adam_fused, wire_direct); nothing about a single call is left on the builder."""
 
     def __init__(self, ctx, params, norm, lane=0):
         self.ctx, self.P, self.norm = ctx, params, norm
@@ -482,7 +525,7 @@ class _Builder:
 
     def fwd_norm_fuse(self, name, a, groups, mean, rstd, act, mask_ptr, update_moving=True):
         """GanNormFuse for the convolution that produces layer `name`'s pre-normalisation output: when the launch is a small
-        split-K one, its slab-reduce kernel also takes the statistics and writes the activation `a` (self.last_full)."""
+        split-K one, its slab-reduce kernel also takes the statistics and writes the activation `a` (ConvPlan.full)."""
         gk, bk = self.norm_names()
         eps = BN_EPS if self.norm == 'batchnorm' else IN_EPS
         mm = mv = None
@@ -500,10 +543,10 @@ class _Builder:
                              self.P.ptr(name + bk, 'grad') if want_param_grads else None, int(accumulate))
 
     def conv(self, op, x, y, w, w_rows, stride=2, bias=None, act=None, y_f32=0, k_real=None, stats_groups=0, bwd_fuse=None, norm_fuse=None):
-        """stats_groups > 0: ask the GEMM epilogue to also emit normalisation-statistics partials; the number of
-        chunks it will write (0 = not fusable for this shape) is left in self.last_stats_chunks.
+        """-> (Op, ConvPlan).  stats_groups > 0: ask the GEMM epilogue to also emit normalisation-statistics partials; the number
+        of chunks it will write (0 = not fusable for this shape) is ConvPlan.stats_chunks.
         bwd_fuse = fuse_spec(...): ask a dgrad launch to start the backward of the layer below in its epilogue;
-        self.last_bwd_fused > 0 (the chunk count for gan_norm_act_bwd_fused) if this launch shape carries it."""
+        ConvPlan.bwd_fused > 0 (the chunk count for gan_norm_act_bwd_fused) if this launch shape carries it."""
         if bwd_fuse is not None and not FUSE_BWD:
             bwd_fuse = None
         if bwd_fuse is not None:
@@ -521,24 +564,23 @@ class _Builder:
         if need + STATS_RESERVE > self.ws_bytes:
             raise L.GanAmdError(f"workspace too small for {op}: need {need}")
         # fused statistics partials live behind the launch's own scratch (split-K slabs) in the lane workspace
-        self.last_stats_ptr = self.ws_ptr + (need + 255) // 256 * 256
+        partial_ptr = self.ws_ptr + (need + 255) // 256 * 256
         if stats_groups:
-            d.stats_partial = self.last_stats_ptr
-            d.stats_partial_bytes = self.ws_bytes - (self.last_stats_ptr - self.ws_ptr)
+            d.stats_partial = partial_ptr
+            d.stats_partial_bytes = self.ws_bytes - (partial_ptr - self.ws_ptr)
         info = (C.c_int32 * 5)()
         self.lib.gan_conv_plan_info(C.byref(d), opi, info)
-        self.last_bwd_fused = 0
-        self.last_full = info[4] == -1       # GanNormFuse honoured: the launch finishes the layer (no norm ops follow)
-        if not self.last_full:               # a request is either honoured or dropped HERE: the library refuses one it cannot honour
+        stats_chunks = bwd_fused = 0
+        full = info[4] == -1                 # GanNormFuse honoured: the launch finishes the layer (no norm ops follow)
+        if not full:                         # a request is either honoured or dropped HERE: the library refuses one it cannot honour
             d.norm_fuse = None
         if bwd_fuse is not None:
-            self.last_stats_chunks = 0
-            self.last_bwd_fused = max(info[4], 0)
+            bwd_fused = max(info[4], 0)
             if not info[4]:            # this launch shape (thin kernel, odd group size ...) cannot carry it: plain dgrad
                 d.bwd_fuse = None
                 d.stats_partial, d.stats_groups = None, 0
         else:
-            self.last_stats_chunks = max(info[4], 0) if stats_groups else 0
+            stats_chunks = max(info[4], 0) if stats_groups else 0
             if stats_groups and not info[4]:
                 d.stats_partial, d.stats_groups = None, 0
         T = 4 if info[3] == 4 else 16
@@ -554,34 +596,34 @@ class _Builder:
         meta = dict(kind='gemm', kernel=kname, flops=flops, splits=info[2],
                     shape=f"{op} M{M}{'x4' if info[3] == 4 else ''} N{y.c} K{T * x.c} s{info[2]}")
         # a launch that finishes its layer (GanNormFuse) on a small tile may join a layer stack (merge_stacks below)
-        if self.last_full and self.lib.gan_conv_stack_eligible(C.byref(d), opi) == 1:
+        if full and self.lib.gan_conv_stack_eligible(C.byref(d), opi) == 1:
             meta['stack'] = (d, opi)
-        return (fn, (self._desc(d),), op, meta)
+        return Op(fn, (self._desc(d),), op, meta), ConvPlan(full, stats_chunks, bwd_fused, partial_ptr)
 
     def wgrad(self, big, small, dw_ptr, big_c, small_c, stride, accumulate, adam_fuse=None, wire_ptr=None, ws_ptr=None, alt=False):
-        """adam_fuse: a GanAdamFuse - ask the launch to apply the optimiser step itself; self.last_adam_fused tells whether it will.
+        """-> (Op, adam_fused, wire_direct).
+        adam_fuse: a GanAdamFuse - ask the launch to apply the optimiser step itself; adam_fused tells whether it will.
         wire_ptr: this kernel's place in the bf16 wire buffer of the data-parallel exchange - ask the launch to write the gradient
-        there (GanWgradDesc.dw_wire); self.last_wire_direct tells whether it will (then dw stays untouched)."""
+        there (GanWgradDesc.dw_wire); wire_direct tells whether it will (then dw stays untouched)."""
         if adam_fuse is not None:
             self.keep.append(adam_fuse)
         d = L.GanWgradDesc(self.ctx.dt, stride, big, small, dw_ptr, big_c, small_c, int(accumulate),
                            ws_ptr or self.ws_side_ptr, self.ws_bytes, int(self.wgrad_concurrent),
                            C.addressof(adam_fuse) if adam_fuse is not None else None, wire_ptr if (wire_ptr and not accumulate and adam_fuse is None) else None)
-        self.last_wire_direct = False
+        wire_direct = adam_fused = False
         if d.dw_wire:
             rc = self.lib.gan_wgrad_wire_direct(C.byref(d))
             if rc < 0:
                 L.check(rc, "wgrad_wire_direct")
-            self.last_wire_direct = rc == 1
-            if not self.last_wire_direct:
+            wire_direct = rc == 1
+            if not wire_direct:
                 d.dw_wire = None
-        self.last_adam_fused = False
         if adam_fuse is not None:
             rc = self.lib.gan_wgrad_adam_fused(C.byref(d))
             if rc < 0:
                 L.check(rc, "wgrad_adam_fused")
-            self.last_adam_fused = rc == 1
-            if not self.last_adam_fused:
+            adam_fused = rc == 1
+            if not adam_fused:
                 d.adam_fuse = None
         need = self.lib.gan_wgrad_workspace_bytes(C.byref(d))
         if need > self.ws_bytes:
@@ -591,7 +633,7 @@ class _Builder:
         flops = 2.0 * small.n * small.h * small.w * 16 * big_c * small_c
         meta = dict(kind='gemm', kernel=f"wgrad<{self.ctx.dtype},{info[0]},{info[1]}>", flops=flops, splits=info[2], alt=bool(alt),
                     shape=f"wgrad A{big_c} B{small_c} M{small.n * small.h * small.w} s{info[2]}")
-        return (self.lib.gan_conv_wgrad, (self._desc(d),), "conv_wgrad", meta, True)      # True: side-stream op
+        return Op(self.lib.gan_conv_wgrad, (self._desc(d),), "conv_wgrad", meta, side=True), adam_fused, wire_direct
 
     def norm_names(self):
         return ('.gamma', '.beta') if self.norm == 'batchnorm' else ('.scale', '.offset')
@@ -613,14 +655,14 @@ class _Builder:
             df.workspace = fused_ptr or self.ws_ptr
             if one:
                 df.workspace_bytes = self.ws_bytes - (df.workspace - self.ws_ptr)
-                return [(self.lib.gan_norm_finalize_act_fwd, (self._desc(df), fused_chunks), f"norm_fin_act_fwd({name})")]
-            return [(self.lib.gan_norm_stats_finalize, (self._desc(df), fused_chunks), f"norm_stats_finalize({name})"),
-                    (self.lib.gan_norm_act_fwd, (r,), f"norm_act_fwd({name})")]
+                return [Op(self.lib.gan_norm_finalize_act_fwd, (self._desc(df), fused_chunks), f"norm_fin_act_fwd({name})")]
+            return [Op(self.lib.gan_norm_stats_finalize, (self._desc(df), fused_chunks), f"norm_stats_finalize({name})"),
+                    Op(self.lib.gan_norm_act_fwd, (r,), f"norm_act_fwd({name})")]
         if one:
-            return [(self.lib.gan_norm_stats_partial, (r,), f"norm_stats_partial({name})"),
-                    (self.lib.gan_norm_finalize_act_fwd, (r, 0), f"norm_fin_act_fwd({name})")]
-        return [(self.lib.gan_norm_stats, (r,), f"norm_stats({name})"),
-                (self.lib.gan_norm_act_fwd, (r,), f"norm_act_fwd({name})")]
+            return [Op(self.lib.gan_norm_stats_partial, (r,), f"norm_stats_partial({name})"),
+                    Op(self.lib.gan_norm_finalize_act_fwd, (r, 0), f"norm_fin_act_fwd({name})")]
+        return [Op(self.lib.gan_norm_stats, (r,), f"norm_stats({name})"),
+                Op(self.lib.gan_norm_act_fwd, (r,), f"norm_act_fwd({name})")]
 
     def norm_bwd(self, name, y, da, da2, dy, groups, mean_ptr, rstd_ptr, act, mask_ptr, want_param_grads, accumulate):
         gk, bk = self.norm_names()
@@ -631,7 +673,7 @@ class _Builder:
                              self.P.ptr(name + gk, 'grad') if want_param_grads else None,
                              self.P.ptr(name + bk, 'grad') if want_param_grads else None,
                              int(accumulate), self.ws_ptr, self.ws_bytes, self.ctx.new_sync())
-        return (self.lib.gan_norm_act_bwd, (self._desc(d),), f"norm_act_bwd({name})")
+        return Op(self.lib.gan_norm_act_bwd, (self._desc(d),), f"norm_act_bwd({name})")
 
     def norm_bwd_fused(self, name, y, dz, dy, groups, mean_ptr, rstd_ptr, chunks, partial_ptr, want_param_grads, accumulate):
         """Second half (finalize + apply) of a layer backward whose first half ran in the producing dgrad's epilogue."""
@@ -642,20 +684,40 @@ class _Builder:
                              self.P.ptr(name + gk, 'grad') if want_param_grads else None,
                              self.P.ptr(name + bk, 'grad') if want_param_grads else None,
                              int(accumulate), partial_ptr, self.ws_bytes - (partial_ptr - self.ws_ptr), self.ctx.new_sync())
-        return (self.lib.gan_norm_act_bwd_fused, (self._desc(d), chunks), f"norm_act_bwd_fused({name})")
+        return Op(self.lib.gan_norm_act_bwd_fused, (self._desc(d), chunks), f"norm_act_bwd_fused({name})")
 
     def act_bwd(self, a, da, da2, dy, act):
         z = L.GanTensor(None, 0, 0, 0, 0, 0)
         d = L.GanActBwdDesc(self.ctx.dt, a, da, da2 if da2 is not None else z, dy, L.ACTS[act], LEAKY_ALPHA, None, 0,
                             self.ws_ptr, self.ws_bytes)
-        return (self.lib.gan_act_bwd, (self._desc(d),), "act_bwd")
+        return Op(self.lib.gan_act_bwd, (self._desc(d),), "act_bwd")
 
     def bias_grad(self, dy, dbias_ptr, accumulate, side=False):
         """side: a side-stream op like the wgrad GEMMs (it only feeds Adam): scratch in the wgrad lane's workspace."""
         self.keep.append(dy)
-        op = (self.lib.gan_bias_grad, (self.ctx.dt, C.byref(dy), dbias_ptr, int(accumulate), self.ws_side_ptr if side else self.ws_ptr,
-                                       self.ws_bytes), "bias_grad")
-        return op + (dict(kind='side', kernel='bias_grad', flops=0.0, shape='bias'), True) if side else op
+        op = Op(self.lib.gan_bias_grad, (self.ctx.dt, C.byref(dy), dbias_ptr, int(accumulate), self.ws_side_ptr if side else self.ws_ptr,
+                                         self.ws_bytes), "bias_grad")
+        return op._replace(meta=dict(kind='side', kernel='bias_grad', flops=0.0, shape='bias'), side=True) if side else op
+
+    def conv_norm_fwd(self, op, x, y, a, w, w_rows, stride, name, groups, mean, rstd, act, mask_ptr):
+        """The convolution `op` that produces layer `name` (pre-normalisation output y, activation a), followed by the layer's
+        norm_fwd ops unless the launch finished the layer itself; the partials are read where the launch left them."""
+        cop, plan = self.conv(op, x, y, w, w_rows, stride, stats_groups=groups,
+                              norm_fuse=self.fwd_norm_fuse(name, a, groups, mean, rstd, act, mask_ptr))
+        if plan.full:
+            return [cop]
+        return [cop] + self.norm_fwd(name, y, a, groups, mean, rstd, act, mask_ptr, fused_chunks=plan.stats_chunks, fused_ptr=plan.partial_ptr)
+
+    def norm_bwd_below(self, above, name, y, da, da2, dz, dy, groups, mean_ptr, rstd_ptr, act, mask_ptr, want_param_grads, accumulate):
+        """What is left of layer `name`'s backward behind the dgrad that produced the gradient w.r.t. its activation (`above`: that
+        launch's ConvPlan): nothing when its slab-reduce kernel finished the layer (GanNormFuse); finalize + apply on dz when its
+        epilogue started it (GanBwdFuse); otherwise the whole normalisation backward of da (+ da2)."""
+        if above.full:
+            return []
+        if above.bwd_fused:
+            return [self.norm_bwd_fused(name, y, dz, dy, groups, mean_ptr, rstd_ptr, above.bwd_fused, above.partial_ptr,
+                                        want_param_grads, accumulate)]
+        return [self.norm_bwd(name, y, da, da2, dy, groups, mean_ptr, rstd_ptr, act, mask_ptr, want_param_grads, accumulate)]
 
 
 class _Stack:
@@ -688,19 +750,19 @@ def merge_stacks(ctx, ops):
 
     def flush():
         if len(run) >= 2:
-            st = _Stack(ctx, [o[3]['stack'] for o in run])
+            st = _Stack(ctx, [o.meta['stack'] for o in run])
             if st.rc:
                 L.check(st.rc, "conv_stack_plan")        # (every layer answered gan_conv_stack_eligible() == 1: a failure here is an error)
             if st.rc == 0:
-                meta = dict(kind='gemm', kernel=f"conv_stack<{ctx.dtype},{len(run)} layers>", flops=sum(o[3]['flops'] for o in run), splits=0,
-                            shape="stack: " + " | ".join(o[3]['shape'] for o in run), keep=(st, list(run)))
-                out.append((ctx.lib.gan_conv_stack_launch, st.args, "conv_stack", meta))
+                meta = dict(kind='gemm', kernel=f"conv_stack<{ctx.dtype},{len(run)} layers>", flops=sum(o.meta['flops'] for o in run), splits=0,
+                            shape="stack: " + " | ".join(o.meta['shape'] for o in run), keep=(st, list(run)))
+                out.append(Op(ctx.lib.gan_conv_stack_launch, st.args, "conv_stack", meta))
                 run.clear()
                 return
         out.extend(run)
         run.clear()
     for o in ops:
-        if len(o) > 3 and isinstance(o[3], dict) and 'stack' in o[3] and not (len(o) > 4 and o[4]):
+        if 'stack' in o.meta and not o.side:
             run.append(o)
         else:
             flush()
@@ -797,7 +859,7 @@ class GenCall:
                                (C.c_uint32 * 3)(*[stream_id * 8 + j for j in range(3)]))
             # per-call launch counter (advanced by the kernel): validation passes draw new masks although the Adam step stands still
             self.mask_draws = torch.zeros(2, dtype=torch.int32, device=dev)
-            self.mask_ops.append((ctx.lib.gan_dropout_mask_multi, (3, self._mask_args[0], self._mask_args[1], seed, P.step.data_ptr(),
+            self.mask_ops.append(Op(ctx.lib.gan_dropout_mask_multi, (3, self._mask_args[0], self._mask_args[1], seed, P.step.data_ptr(),
                                                                    self._mask_args[2], self.mask_draws.data_ptr()), "dropout_mask_multi"))
         self.auto_masks = dropout
 
@@ -816,14 +878,11 @@ class GenCall:
                 self.fwd_inner_start = len(fwd)      # from here on (M <= 4096 rows) the layers leave most of the chip idle
             w = P.tr[name + '.kernel']
             if i == 0:      # conv -> LeakyReLU fused in the GEMM epilogue (apply_norm=False, base_gan.py:180)
-                fwd.append(bd.conv('conv_fwd', x, a_down(0), w.data_ptr(), G_DOWN[0], 2, None, 'lrelu', k_real=C_))
+                fwd.append(bd.conv('conv_fwd', x, a_down(0), w.data_ptr(), G_DOWN[0], 2, None, 'lrelu', k_real=C_)[0])
             else:
                 mean, rstd = stat(name, G_DOWN[i])
-                fwd.append(bd.conv('conv_fwd', x, self.y_down[i].view(), w.data_ptr(), G_DOWN[i], 2, stats_groups=groups,
-                                   norm_fuse=bd.fwd_norm_fuse(name, a_down(i), groups, mean, rstd, 'lrelu', None)))
-                if not bd.last_full:
-                    fwd += bd.norm_fwd(name, self.y_down[i].view(), a_down(i), groups, mean, rstd, 'lrelu', None,
-                                       fused_chunks=bd.last_stats_chunks, fused_ptr=bd.last_stats_ptr)
+                fwd += bd.conv_norm_fwd('conv_fwd', x, self.y_down[i].view(), a_down(i), w.data_ptr(), G_DOWN[i], 2, name, groups, mean, rstd,
+                                        'lrelu', None)
             x = a_down(i)
         for j in range(7):
             name = f'up{j}'
@@ -831,13 +890,10 @@ class GenCall:
             w = P.nat[name + '.kernel']
             mean, rstd = stat(name, G_UP[j])
             mptr = self.masks[j].data_ptr() if (dropout and j < 3) else None
-            fwd.append(bd.conv('convT_fwd', xin, self.y_up[j].view(), w.data_ptr(), G_UP[j], 2, stats_groups=groups,
-                               norm_fuse=bd.fwd_norm_fuse(name, self.cat[j].view(0, G_UP[j]), groups, mean, rstd, 'relu', mptr)))
-            if not bd.last_full:
-                fwd += bd.norm_fwd(name, self.y_up[j].view(), self.cat[j].view(0, G_UP[j]), groups, mean, rstd, 'relu', mptr,
-                                   fused_chunks=bd.last_stats_chunks, fused_ptr=bd.last_stats_ptr)
+            fwd += bd.conv_norm_fwd('convT_fwd', xin, self.y_up[j].view(), self.cat[j].view(0, G_UP[j]), w.data_ptr(), G_UP[j], 2, name, groups,
+                                    mean, rstd, 'relu', mptr)
         fwd.append(bd.conv('convT_fwd', self.cat[6].view(), self.out.view(0, C_), P.nat['last.kernel'].data_ptr(), C_, 2,
-                           P.ptr('last.bias'), 'tanh'))
+                           P.ptr('last.bias'), 'tanh')[0])
         head = merge_stacks(ctx, fwd[:self.fwd_inner_start])
         self.fwd_ops = head + merge_stacks(ctx, fwd[self.fwd_inner_start:])
         self.fwd_inner_start = len(head)
@@ -854,9 +910,8 @@ class GenCall:
             self.dgen2 = Buf(ctx, B, S, S, 8)     # upstream gradient slot 2 (e.g. from the discriminator)
             self.dxin = Buf(ctx, B, S, S, 8)
         self.fold_ops = []                        # (the inference-call surface of GenEvalCall: InstanceNorm has nothing to fold)
-        self._bwd_cache = {}
-        self.adam_fused = {}
-        self.wire_direct = {}
+        self._bwd_cache = {}                      # BwdKey -> BwdPlan (empty: no backward list has been built yet)
+        self._bwd_split = {}                      # (BwdKey, 'all' | stage bounds) -> that plan's ops with layer stacks merged / in stages
         # Options of the step object (Pix2PixStep._settle_gen_options), settled before the first backward op list is built: the kernels
         # whose wgrad launch runs on a SECOND wgrad lane (own slab workspace) in the staged schedule; the head's bias gradient as a
         # side-stream op
@@ -871,9 +926,9 @@ class GenCall:
         takes them; 'wide' - a host call: one wgrad GEMM per layer over its own AND its guest's samples, plain write (the guest's
         saved activations and output gradients must be in place: its forward and its backward(wgrads='none') have run).
         adam = (beta_1, beta_2): every wgrad launch that can applies this step's Adam update to its kernel itself (GanAdamFuse;
-        needs plain-write kernel gradients: wgrads 'own' without accumulate, or 'wide'); self.adam_fused[key] lists those kernels.
+        needs plain-write kernel gradients: wgrads 'own' without accumulate, or 'wide'); BwdPlan.adam_fused lists those kernels.
         wire = data pointer of this network's bf16 wire buffer (data-parallel exchange, ParamSet offsets): every wgrad launch that can
-        writes its gradient there in the wire format instead of the fp32 buffer (GanWgradDesc.dw_wire); self.wire_direct[key] lists
+        writes its gradient there in the wire format instead of the fp32 buffer (GanWgradDesc.dw_wire); BwdPlan.wire_direct lists
         those kernels - the caller casts (gan_grad_pack) only the rest of a bucket.
         The caller runs gan_adam_begin BEFORE this list and ParamSet.adam_rest_ops() for everything else after it, and must not
         start a layer's wgrad before every dgrad of the step that reads the layer's weights has been enqueued (staged order).
@@ -896,12 +951,18 @@ class GenCall:
             af = P.adam_fuse_desc(kname, adam[0], adam[1]) if adam is not None else None
             wp = wire + 2 * P.entries[kname][0] if wire else None
             alt = kname in self.alt_wgrad
-            ops.append(bd.wgrad(big_v, small_v, P.ptr(kname, 'grad'), big_c, small_c, stride, wacc, adam_fuse=af, wire_ptr=wp,
-                                ws_ptr=self.ctx.ws_lanes[5].data_ptr() if alt else None, alt=alt))
-            if af is not None and bd.last_adam_fused:
+            op, adam_fused, wire_direct = bd.wgrad(big_v, small_v, P.ptr(kname, 'grad'), big_c, small_c, stride, wacc, adam_fuse=af, wire_ptr=wp,
+                                                   ws_ptr=self.ctx.ws_lanes[5].data_ptr() if alt else None, alt=alt)
+            ops.append(op)
+            if adam_fused:
                 fused_names.append(kname)
-            if bd.last_wire_direct:
+            if wire_direct:
                 wire_names.append(kname)
+
+        def dgrad(*args, **kw):       # -> the launch's ConvPlan: what is left of the backward of the layer below
+            op, plan = bd.conv(*args, **kw)
+            ops.append(op)
+            return plan
         ops = []
         ops.append(bd.act_bwd(self.out.view(), self.dgen.view(), self.dgen2.view() if use_dgen2 else None,
                               self.dpre.view(), 'tanh'))
@@ -914,21 +975,15 @@ class GenCall:
             return bd.fuse_spec(self.y_up[j].view(), None, f'up{j}', groups, mean.data_ptr(), rstd.data_ptr(), 'relu', mptr, 512,
                                 cols=G_UP[j])
 
-        ops.append(bd.conv('convT_dgrad', self.dpre.view(), self.dcat[6].view(), P.tr['last.kernel'].data_ptr(), 128, 2, k_real=C_,
-                           bwd_fuse=up_spec(6)))
-        fused, fptr, full = bd.last_bwd_fused, bd.last_stats_ptr, False
+        above = dgrad('convT_dgrad', self.dpre.view(), self.dcat[6].view(), P.tr['last.kernel'].data_ptr(), 128, 2, k_real=C_,
+                      bwd_fuse=up_spec(6))
         for j in range(6, -1, -1):
             name = f'up{j}'
             mean, rstd = self.stats[name]
             mptr = self.masks[j].data_ptr() if (self.masks is not None and j < 3) else None
-            if full:         # the dgrad above finished this layer's backward in its slab-reduce kernel (GanNormFuse)
-                pass
-            elif fused:
-                ops.append(bd.norm_bwd_fused(name, self.y_up[j].view(), self.dcat[j].view(0, G_UP[j]), self.dy_up[j].view(), groups,
-                                             mean.data_ptr(), rstd.data_ptr(), fused, fptr, True, accumulate))
-            else:
-                ops.append(bd.norm_bwd(name, self.y_up[j].view(), self.dcat[j].view(0, G_UP[j]), None, self.dy_up[j].view(),
-                                       groups, mean.data_ptr(), rstd.data_ptr(), 'relu', mptr, True, accumulate))
+            dz = self.dcat[j].view(0, G_UP[j])
+            ops += bd.norm_bwd_below(above, name, self.y_up[j].view(), dz, None, dz, self.dy_up[j].view(), groups,
+                                     mean.data_ptr(), rstd.data_ptr(), 'relu', mptr, True, accumulate)
             xin = self.a7 if j == 0 else self.cat[j - 1]
             dxin = self.da7 if j == 0 else self.dcat[j - 1]
             cin = xin.c
@@ -939,62 +994,40 @@ class GenCall:
                 m7, r7 = self.stats['down7']
                 spec = bd.fuse_spec(self.y_down[7].view(), None, 'down7', groups, m7.data_ptr(), r7.data_ptr(), 'lrelu')
                 nfz = bd.bwd_norm_fuse('down7', self.dy_down[7].view(), True, accumulate)
-            ops.append(bd.conv('convT_dgrad', self.dy_up[j].view(), dxin.view(), P.tr[name + '.kernel'].data_ptr(), cin, 2, bwd_fuse=spec,
-                               norm_fuse=nfz))
-            fused, fptr, full = bd.last_bwd_fused, bd.last_stats_ptr, bd.last_full
-        dy0 = self.dy_down[0]
-        for i in range(7, -1, -1):
+            above = dgrad('convT_dgrad', self.dy_up[j].view(), dxin.view(), P.tr[name + '.kernel'].data_ptr(), cin, 2, bwd_fuse=spec,
+                          norm_fuse=nfz)
+        for i in range(7, 0, -1):
             name = f'down{i}'
             if i == 7:
-                da, da2 = self.da7.view(), None
+                da, da2, dz = self.da7.view(), None, self.da7.view()
             else:
                 j = 6 - i
-                da, da2 = self.dcat[j].view(G_UP[j], G_DOWN[i]), self.dA[i].view()
-            if i == 0:
-                if fused:
-                    dy0 = self.dA[0]        # the epilogue of down1's dgrad already applied LeakyReLU' and the skip gradient
-                else:
-                    ops.append(bd.act_bwd(self.cat[6].view(G_UP[6], 64), da, da2, self.dy_down[0].view(), 'lrelu'))
+                da, da2, dz = self.dcat[j].view(G_UP[j], G_DOWN[i]), self.dA[i].view(), self.dA[i].view()
+            mean, rstd = self.stats[name]
+            ops += bd.norm_bwd_below(above, name, self.y_down[i].view(), da, da2, dz, self.dy_down[i].view(), groups,
+                                     mean.data_ptr(), rstd.data_ptr(), 'lrelu', None, True, accumulate)
+            jb = 6 - (i - 1)                                         # layer below: down i-1, its activation and skip gradient sit in cat / dcat[jb]
+            wgrad(W(self.cat[jb]).view(G_UP[jb], G_DOWN[i - 1]), W(self.dy_down[i]).view(), name + '.kernel', G_DOWN[i - 1], G_DOWN[i], 2)
+            skip = self.dcat[jb].view(G_UP[jb], G_DOWN[i - 1])
+            if i - 1 == 0:
+                spec = bd.fuse_spec(self.cat[6].view(G_UP[6], 64), skip, None, act='lrelu')
             else:
-                mean, rstd = self.stats[name]
-                if full:
-                    pass
-                elif fused:
-                    dz = self.da7.view() if i == 7 else self.dA[i].view()
-                    ops.append(bd.norm_bwd_fused(name, self.y_down[i].view(), dz, self.dy_down[i].view(), groups,
-                                                 mean.data_ptr(), rstd.data_ptr(), fused, fptr, True, accumulate))
-                else:
-                    ops.append(bd.norm_bwd(name, self.y_down[i].view(), da, da2, self.dy_down[i].view(), groups,
-                                           mean.data_ptr(), rstd.data_ptr(), 'lrelu', None, True, accumulate))
-            dyi = dy0 if i == 0 else self.dy_down[i]
-            if i == 0:
-                xin, cin_real = W(self.xin).view(), C_
-                self.dy0_in_dA = dy0 is self.dA[0]        # (host and guest must agree on where down0's output gradient lives)
-            elif i == 1:
-                xin, cin_real = W(self.cat[6]).view(G_UP[6], 64), 64
-            else:
-                jj = 6 - (i - 1)
-                xin, cin_real = W(self.cat[jj]).view(G_UP[jj], G_DOWN[i - 1]), G_DOWN[i - 1]
-            wgrad(xin, W(dyi).view(), name + '.kernel', cin_real, G_DOWN[i], 2)
-            fused, full = 0, False
-            if i > 0:
-                jb = 6 - (i - 1)                                     # layer below: down i-1, its skip gradient sits in dcat[jb]
-                skip = self.dcat[jb].view(G_UP[jb], G_DOWN[i - 1])
-                if i - 1 == 0:
-                    spec = bd.fuse_spec(self.cat[6].view(G_UP[6], 64), skip, None, act='lrelu')
-                else:
-                    mb, rb = self.stats[f'down{i - 1}']
-                    spec = bd.fuse_spec(self.y_down[i - 1].view(), skip, f'down{i - 1}', groups, mb.data_ptr(), rb.data_ptr(), 'lrelu')
-                ops.append(bd.conv('conv_dgrad', dyi.view(), self.dA[i - 1].view(),
-                                   P.nat[name + '.kernel'].data_ptr(), G_DOWN[i - 1], 2, bwd_fuse=spec,
-                                   norm_fuse=bd.bwd_norm_fuse(f'down{i - 1}', self.dy_down[i - 1].view(), True, accumulate) if i - 1 > 0 else None))
-                fused, fptr, full = bd.last_bwd_fused, bd.last_stats_ptr, bd.last_full
-            elif need_dx:
-                ops.append(bd.conv('conv_dgrad', dyi.view(), self.dxin.view(0, C_),
-                                   P.nat[name + '.kernel'].data_ptr(), C_, 2))
-        self.adam_fused[(use_dgen2, need_dx, accumulate, wgrads, adam)] = tuple(fused_names)
-        self.wire_direct[(use_dgen2, need_dx, accumulate, wgrads, adam, wire)] = tuple(wire_names)
-        return ops
+                mb, rb = self.stats[f'down{i - 1}']
+                spec = bd.fuse_spec(self.y_down[i - 1].view(), skip, f'down{i - 1}', groups, mb.data_ptr(), rb.data_ptr(), 'lrelu')
+            above = dgrad('conv_dgrad', self.dy_down[i].view(), self.dA[i - 1].view(),
+                          P.nat[name + '.kernel'].data_ptr(), G_DOWN[i - 1], 2, bwd_fuse=spec,
+                          norm_fuse=bd.bwd_norm_fuse(f'down{i - 1}', self.dy_down[i - 1].view(), True, accumulate) if i - 1 > 0 else None)
+        # down0: activation only.  Where the epilogue of down1's dgrad already applied LeakyReLU' and the skip gradient, its output
+        # gradient lives in dA[0] (host and guest must agree on that: BwdPlan.dy0_in_dA)
+        dy0_in_dA = bool(above.bwd_fused)
+        dy0 = self.dA[0] if dy0_in_dA else self.dy_down[0]
+        if not dy0_in_dA:
+            ops.append(bd.act_bwd(self.cat[6].view(G_UP[6], 64), self.dcat[6].view(G_UP[6], G_DOWN[0]), self.dA[0].view(),
+                                  self.dy_down[0].view(), 'lrelu'))
+        wgrad(W(self.xin).view(), W(dy0).view(), 'down0.kernel', C_, G_DOWN[0], 2)
+        if need_dx:
+            ops.append(bd.conv('conv_dgrad', dy0.view(), self.dxin.view(0, C_), P.nat['down0.kernel'].data_ptr(), C_, 2)[0])
+        return BwdPlan(ops, fused_names, wire_names, dy0_in_dA)
 
     # public API ------------------------------------------------------------------------------
     def set_dropmasks(self, masks):
@@ -1036,17 +1069,25 @@ class GenCall:
         """Samples [n0, n0 + n) of this call as a call-like object (CycleGAN batches two logical calls of one generator)."""
         return CallSlice(self, n0, n)
 
-    def _bwd_key(self, use_dgen2, need_dx, accumulate, wgrads, adam, wire=None):
-        if wire:
-            return (use_dgen2, need_dx, accumulate, wgrads, adam, wire)
-        return (use_dgen2, need_dx, accumulate) if wgrads == 'own' and adam is None else (use_dgen2, need_dx, accumulate, wgrads, adam)
+    def bwd_plan(self, use_dgen2=False, need_dx=False, accumulate=False, wgrads='own', adam=None, wire=None):
+        """The (cached) BwdPlan of one backward build: the op list, with the kernels whose wgrad carries Adam / writes the wire
+        format and where down0's output gradient lives.  Arguments: see _build_bwd."""
+        return self._bwd(BwdKey(use_dgen2, need_dx, accumulate, wgrads, adam, wire or None))
+
+    def _bwd(self, key):
+        if key not in self._bwd_cache:
+            self._bwd_cache[key] = self._build_bwd(*key)
+        return self._bwd_cache[key]
+
+    @property
+    def adam_fused(self):
+        """{BwdKey: the kernels whose wgrad launch carries Adam} of every backward list built so far."""
+        return {key: plan.adam_fused for key, plan in self._bwd_cache.items()}
 
     def backward(self, use_dgen2=False, need_dx=False, accumulate=False, defer_wgrads=False, wgrads='own', adam=None):
         """Upstream gradient(s) w.r.t. the tanh output must be in self.dgen (and self.dgen2).  wgrads / adam: see _build_bwd."""
-        key = self._bwd_key(use_dgen2, need_dx, accumulate, wgrads, adam)
-        if key not in self._bwd_cache:
-            self._bwd_cache[key] = self._build_bwd(*key)
-        ops = self._bwd_cache[key]
+        key = BwdKey(use_dgen2, need_dx, accumulate, wgrads, adam)
+        ops = self._bwd(key)
         if defer_wgrads == 'staged':
             # the wgrad GEMMs (they only feed Adam) run on `self.wgrad_stream` in a few coarse stages: those of the
             # layers before cut k start when the main dgrad/norm chain has passed cut k - per-op dependencies thrash
@@ -1056,40 +1097,30 @@ class GenCall:
                 self.ctx.run(main_ops)
                 self.wgrad_stream.wait_stream(main)
                 two = self.wgrad_stream2 is not None
-                w2 = [o for o in w_ops if two and o[3].get('alt')]
-                self.ctx.run_on([o for o in w_ops if not (two and o[3].get('alt'))], self.wgrad_stream)
+                w2 = [o for o in w_ops if two and o.meta.get('alt')]
+                self.ctx.run_on([o for o in w_ops if not (two and o.meta.get('alt'))], self.wgrad_stream)
                 if w2:           # second wgrad lane (forked from the origin stream, like every side lane)
                     self.wgrad_stream2.wait_stream(main)
                     self.ctx.run_on(w2, self.wgrad_stream2)
         else:
-            mkey = ('all', key)
-            if mkey not in self._bwd_cache:
-                self._bwd_cache[mkey] = merge_stacks(self.ctx, ops)      # (adjacent launches only: wgrads between two dgrads end a run)
-            self.ctx.run(self._bwd_cache[mkey])
-
-    def bwd_ops(self, use_dgen2=False, need_dx=False, accumulate=False, wgrads='own', adam=None):
-        """The (cached) backward op list; building it also settles self.dy0_in_dA and self.adam_fused."""
-        key = self._bwd_key(use_dgen2, need_dx, accumulate, wgrads, adam)
-        if key not in self._bwd_cache:
-            self._bwd_cache[key] = self._build_bwd(*key)
-        return self._bwd_cache[key]
+            mkey = (key, 'all')
+            if mkey not in self._bwd_split:
+                self._bwd_split[mkey] = merge_stacks(self.ctx, ops)      # (adjacent launches only: wgrads between two dgrads end a run)
+            self.ctx.run(self._bwd_split[mkey])
 
     def bwd_stages(self, cuts, use_dgen2=False, need_dx=False, accumulate=False, wgrads='own', adam=None, wire=None):
         """The backward op list cut into coarse stages at the wgrad indices `cuts` (the same cuts as the 'staged'
         mode): [(main-chain ops, wgrad ops)] per stage.  The wgrad GEMMs of a stage only feed Adam, so a caller may
         run them beside the NEXT stage's main chain (gan_amd/steps.py data-parallel schedule)."""
-        key = self._bwd_key(use_dgen2, need_dx, accumulate, wgrads, adam, wire)
-        if key not in self._bwd_cache:
-            self._bwd_cache[key] = self._build_bwd(use_dgen2, need_dx, accumulate, wgrads, adam, wire)
-        ops = self._bwd_cache[key]
-        is_w = lambda o: len(o) > 4 and o[4]
-        idx = [i for i, o in enumerate(ops) if is_w(o) and o[2] == 'conv_wgrad']     # (other side ops ride in the stage they fall into)
+        key = BwdKey(use_dgen2, need_dx, accumulate, wgrads, adam, wire or None)
+        ops = self._bwd(key)
+        idx = [i for i, o in enumerate(ops) if o.side and o.label == 'conv_wgrad']     # (other side ops ride in the stage they fall into)
         bounds = [0] + [idx[c] for c in cuts if 0 < c < len(idx)] + [len(ops)]
-        skey = ('stages', key, tuple(bounds))          # (cached: merged layer stacks hold device plans, built outside any capture)
-        if skey not in self._bwd_cache:
-            self._bwd_cache[skey] = [(merge_stacks(self.ctx, [o for o in ops[lo:hi] if not is_w(o)]), [o for o in ops[lo:hi] if is_w(o)])
+        skey = (key, tuple(bounds))
+        if skey not in self._bwd_split:                # (cached: merged layer stacks hold device plans, built outside any capture)
+            self._bwd_split[skey] = [(merge_stacks(self.ctx, [o for o in ops[lo:hi] if not o.side]), [o for o in ops[lo:hi] if o.side])
                                      for lo, hi in zip(bounds[:-1], bounds[1:])]
-        return self._bwd_cache[skey]
+        return self._bwd_split[skey]
 
     def output_f32(self):
         o = torch.empty((self.B, self.S, self.S, self.C), dtype=torch.float32, device=self.ctx.device)
@@ -1123,7 +1154,7 @@ class FoldedParams:
             tiles += 16 * ((co + 63) // 64) * tk
         arr = (L.GanFoldEntry * len(ents))(*ents)
         self._table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(ctx.device)
-        self.fold_ops = [(ctx.lib.gan_bn_fold_multi, (self._table.data_ptr(), len(ents), tiles, ctx.dt, BN_EPS), "bn_fold_multi")]
+        self.fold_ops = [Op(ctx.lib.gan_bn_fold_multi, (self._table.data_ptr(), len(ents), tiles, ctx.dt, BN_EPS), "bn_fold_multi")]
 
     def fold(self):
         """Refresh the folded weights from the current master, gamma / beta and moving statistics (one launch)."""
@@ -1156,21 +1187,22 @@ class GenEvalCall:
                 return self.a7.view()
             j = 6 - i
             return self.cat[j].view(G_UP[j], G_DOWN[i])
+        conv = lambda *a_, **k_: bd.conv(*a_, **k_)[0]      # (the op alone: a folded layer is finished by its one launch)
         fwd = []
         x = self.xin.view()
         for i in range(8):
             if i == 0:      # no normalisation (base_gan.py:180): as in training mode
-                fwd.append(bd.conv('conv_fwd', x, a_down(0), P.tr['down0.kernel'].data_ptr(), G_DOWN[0], 2, None, 'lrelu', k_real=C_))
+                fwd.append(conv('conv_fwd', x, a_down(0), P.tr['down0.kernel'].data_ptr(), G_DOWN[0], 2, None, 'lrelu', k_real=C_))
             else:           # Conv -> BN (moving statistics) -> LeakyReLU = conv on folded weights + bias + LeakyReLU
                 name = f'down{i}'
-                fwd.append(bd.conv('conv_fwd', x, a_down(i), F.nk[name].data_ptr(), G_DOWN[i], 2, F.bias[name].data_ptr(), 'lrelu'))
+                fwd.append(conv('conv_fwd', x, a_down(i), F.nk[name].data_ptr(), G_DOWN[i], 2, F.bias[name].data_ptr(), 'lrelu'))
             x = a_down(i)
         for j in range(7):  # ConvT -> BN -> [Dropout: identity] -> ReLU, into the leading channels of the concat buffer
             name = f'up{j}'
             xin = self.a7.view() if j == 0 else self.cat[j - 1].view()
-            fwd.append(bd.conv('convT_fwd', xin, self.cat[j].view(0, G_UP[j]), F.nk[name].data_ptr(), G_UP[j], 2, F.bias[name].data_ptr(), 'relu'))
-        fwd.append(bd.conv('convT_fwd', self.cat[6].view(), self.out.view(0, C_), P.nat['last.kernel'].data_ptr(), C_, 2,
-                           P.ptr('last.bias'), 'tanh'))
+            fwd.append(conv('convT_fwd', xin, self.cat[j].view(0, G_UP[j]), F.nk[name].data_ptr(), G_UP[j], 2, F.bias[name].data_ptr(), 'relu'))
+        fwd.append(conv('convT_fwd', self.cat[6].view(), self.out.view(0, C_), P.nat['last.kernel'].data_ptr(), C_, 2,
+                        P.ptr('last.bias'), 'tanh'))
         self.fold_ops = F.fold_ops
         self.fwd_ops = fwd
         self.ops = self.fold_ops + self.fwd_ops
@@ -1276,18 +1308,15 @@ class DiscCall:
         dev, f32 = ctx.device, torch.float32
         self.stats = {k: (torch.zeros(groups * c, dtype=f32, device=dev), torch.zeros(groups * c, dtype=f32, device=dev))
                       for k, c in [('down1', 128), ('down2', 256), ('conv', 512)]}
-        fwd = [bd.conv('conv_fwd', self.xin.view(), self.a0.view(), P.tr['down0.kernel'].data_ptr(), 64, 2, None, 'lrelu', k_real=net.cin)]
+        fwd = [bd.conv('conv_fwd', self.xin.view(), self.a0.view(), P.tr['down0.kernel'].data_ptr(), 64, 2, None, 'lrelu', k_real=net.cin)[0]]
         prev = self.a0
         for name, co, stride in self.LAYERS[1:4]:
             mean, rstd = self.stats[name]
-            fwd.append(bd.conv('conv_fwd', prev.view(), self.y[name].view(), P.tr[name + '.kernel'].data_ptr(), co, stride,
-                               stats_groups=groups, norm_fuse=bd.fwd_norm_fuse(name, self.a[name].view(), groups, mean, rstd, 'lrelu', None)))
-            if not bd.last_full:
-                fwd += bd.norm_fwd(name, self.y[name].view(), self.a[name].view(), groups, mean, rstd, 'lrelu', None,
-                                   fused_chunks=bd.last_stats_chunks, fused_ptr=bd.last_stats_ptr)
+            fwd += bd.conv_norm_fwd('conv_fwd', prev.view(), self.y[name].view(), self.a[name].view(), P.tr[name + '.kernel'].data_ptr(), co, stride,
+                                    name, groups, mean, rstd, 'lrelu', None)
             prev = self.a[name]
         fwd.append(bd.conv('conv_fwd', prev.view(), self.logits.view(), P.tr['last.kernel'].data_ptr(), 1, 1,
-                           P.ptr('last.bias'), None, 1))
+                           P.ptr('last.bias'), None, 1)[0])
         self.fwd_ops = merge_stacks(ctx, fwd)        # (runs start after down3: fwd_inner_start stays valid)
         self.fold_ops = []
         self._cache = {}
@@ -1317,20 +1346,16 @@ class DiscCall:
             bd, P, net, B = (self._bd2 if lane == 2 else self._bd), self.net.params, self.net, self.B
             n0, gper = call * B, self.gper
             sv = lambda buf: buf.view(0, None, n0, B)
-            ops = [bd.conv('conv_fwd', sv(self.xin), sv(self.a0), P.tr['down0.kernel'].data_ptr(), 64, 2, None, 'lrelu', k_real=net.cin)]
+            ops = [bd.conv('conv_fwd', sv(self.xin), sv(self.a0), P.tr['down0.kernel'].data_ptr(), 64, 2, None, 'lrelu', k_real=net.cin)[0]]
             prev = self.a0
             for name, co, stride in self.LAYERS[1:4]:
                 mean, rstd = self.stats[name]
                 lo, hi = call * gper * co, (call + 1) * gper * co
-                ops.append(bd.conv('conv_fwd', sv(prev), sv(self.y[name]), P.tr[name + '.kernel'].data_ptr(), co, stride,
-                                   stats_groups=gper,
-                                   norm_fuse=bd.fwd_norm_fuse(name, sv(self.a[name]), gper, mean[lo:hi], rstd[lo:hi], 'lrelu', None)))
-                if not bd.last_full:
-                    ops += bd.norm_fwd(name, sv(self.y[name]), sv(self.a[name]), gper, mean[lo:hi], rstd[lo:hi], 'lrelu', None,
-                                       fused_chunks=bd.last_stats_chunks, fused_ptr=bd.last_stats_ptr)
+                ops += bd.conv_norm_fwd('conv_fwd', sv(prev), sv(self.y[name]), sv(self.a[name]), P.tr[name + '.kernel'].data_ptr(), co, stride,
+                                        name, gper, mean[lo:hi], rstd[lo:hi], 'lrelu', None)
                 prev = self.a[name]
             ops.append(bd.conv('conv_fwd', sv(prev), sv(self.logits), P.tr['last.kernel'].data_ptr(), 1, 1,
-                               P.ptr('last.bias'), None, 1))
+                               P.ptr('last.bias'), None, 1)[0])
             self._cache[key] = merge_stacks(self.ctx, ops)
         return self._cache[key]
 
@@ -1344,17 +1369,23 @@ class DiscCall:
         return self.dlogits.t.data_ptr() + call * per * self.dlogits.t.element_size()
 
     def _chain(self, n0, n, groups, stat_off, wgrads, need_dx, accumulate, dx_dst=None, dx_c0=0, wire=None):
-        """Backward over samples [n0, n0+n).  Scratch gradients always live at samples [0, n) of the dA/dy
+        """Backward over samples [n0, n0+n) -> BwdPlan.  Scratch gradients always live at samples [0, n) of the dA/dy
         buffers; saved forward tensors are read at [n0, n0+n)."""
         bd, P = (self._bd2 if wgrads else self._bd), self.net.params
         ops = []
         wire_names = []
 
         def wg(big_v, small_v, kname, big_c, small_c, stride):
-            ops.append(bd.wgrad(big_v, small_v, P.ptr(kname, 'grad'), big_c, small_c, stride, accumulate,
-                                wire_ptr=wire + 2 * P.entries[kname][0] if wire else None))
-            if bd.last_wire_direct:
+            op, _, wire_direct = bd.wgrad(big_v, small_v, P.ptr(kname, 'grad'), big_c, small_c, stride, accumulate,
+                                          wire_ptr=wire + 2 * P.entries[kname][0] if wire else None)
+            ops.append(op)
+            if wire_direct:
                 wire_names.append(kname)
+
+        def dgrad(*args, **kw):       # -> the launch's ConvPlan: what is left of the backward of the layer below
+            op, plan = bd.conv(*args, **kw)
+            ops.append(op)
+            return plan
         sv = lambda buf: buf.view(0, None, n0, n)          # saved forward tensors
         gv = lambda buf: buf.view(0, None, 0, n)           # gradient scratch
         dl = self.dlogits.view(0, None, n0, n) if wgrads else self.dlogits_b.view()
@@ -1370,59 +1401,44 @@ class DiscCall:
             return bd.fuse_spec(sv(self.y[layer]), None, layer, groups, m_.data_ptr() + 4 * stat_off * c_,
                                 r_.data_ptr() + 4 * stat_off * c_, 'lrelu')
 
-        ops.append(bd.conv('conv_dgrad', dl, gv(self.dA['conv']), P.nat['last.kernel'].data_ptr(), 512, 1, k_real=1,
-                           bwd_fuse=spec_for('conv')))
-        fused, fptr, full = bd.last_bwd_fused, bd.last_stats_ptr, False
+        above = dgrad('conv_dgrad', dl, gv(self.dA['conv']), P.nat['last.kernel'].data_ptr(), 512, 1, k_real=1, bwd_fuse=spec_for('conv'))
         order = [('conv', 'down2', 1, 256), ('down2', 'down1', 2, 128), ('down1', 'down0', 2, 64)]
         for name, prev, stride, cprev in order:
             mean, rstd = self.stats[name]
             c = self.y[name].c
-            if full:
-                pass
-            elif fused:
-                ops.append(bd.norm_bwd_fused(name, sv(self.y[name]), gv(self.dA[name]), gv(self.dy[name]), groups,
-                                             mean.data_ptr() + 4 * stat_off * c, rstd.data_ptr() + 4 * stat_off * c, fused, fptr,
-                                             wgrads, accumulate))
-            else:
-                ops.append(bd.norm_bwd(name, sv(self.y[name]), gv(self.dA[name]), None, gv(self.dy[name]), groups,
-                                       mean.data_ptr() + 4 * stat_off * c, rstd.data_ptr() + 4 * stat_off * c, 'lrelu', None,
-                                       wgrads, accumulate))
+            dz = gv(self.dA[name])
+            ops += bd.norm_bwd_below(above, name, sv(self.y[name]), dz, None, dz, gv(self.dy[name]), groups,
+                                     mean.data_ptr() + 4 * stat_off * c, rstd.data_ptr() + 4 * stat_off * c, 'lrelu', None, wgrads, accumulate)
             if wgrads:
                 wg(sv(self.a[prev]), gv(self.dy[name]), name + '.kernel', cprev, c, stride)
-            ops.append(bd.conv('conv_dgrad', gv(self.dy[name]), gv(self.dA[prev]), P.nat[name + '.kernel'].data_ptr(), cprev, stride,
-                               bwd_fuse=spec_for(prev),
-                               norm_fuse=bd.bwd_norm_fuse(prev, gv(self.dy[prev]), wgrads, accumulate) if prev != 'down0' else None))
-            fused, fptr, full = bd.last_bwd_fused, bd.last_stats_ptr, bd.last_full
-        dy0 = self.dA['down0'] if fused else self.dy['down0']
-        if not fused:
+            above = dgrad('conv_dgrad', gv(self.dy[name]), gv(self.dA[prev]), P.nat[name + '.kernel'].data_ptr(), cprev, stride,
+                          bwd_fuse=spec_for(prev),
+                          norm_fuse=bd.bwd_norm_fuse(prev, gv(self.dy[prev]), wgrads, accumulate) if prev != 'down0' else None)
+        dy0 = self.dA['down0'] if above.bwd_fused else self.dy['down0']
+        if not above.bwd_fused:
             ops.append(bd.act_bwd(sv(self.a0), gv(self.dA['down0']), None, gv(self.dy['down0']), 'lrelu'))
         if wgrads:
             wg(sv(self.xin), gv(dy0), 'down0.kernel', self.net.cin, 64, 2)
         if need_dx:
             if dx_dst is not None:      # only channels [dx_c0, dx_c0 + dx_dst.c) of the input gradient, written where the caller wants them
                 wk = P.nat['down0.kernel']
-                ops.append(bd.conv('conv_dgrad', gv(dy0), dx_dst, wk.data_ptr() + dx_c0 * wk.shape[2] * wk.element_size(), self.net.cin, 2))
+                dgrad('conv_dgrad', gv(dy0), dx_dst, wk.data_ptr() + dx_c0 * wk.shape[2] * wk.element_size(), self.net.cin, 2)
             else:
-                ops.append(bd.conv('conv_dgrad', gv(dy0), self.dxin.view(0, self.net.cin, 0, n),
-                                   P.nat['down0.kernel'].data_ptr(), self.net.cin, 2))
-        if wire:
-            self.wire_direct = tuple(wire_names)
-        return merge_stacks(self.ctx, ops)       # (adjacent launches only: a wgrad between two dgrads ends a run)
+                dgrad('conv_dgrad', gv(dy0), self.dxin.view(0, self.net.cin, 0, n), P.nat['down0.kernel'].data_ptr(), self.net.cin, 2)
+        # (merged stacks: adjacent launches only, a wgrad between two dgrads ends a run)
+        return BwdPlan(merge_stacks(self.ctx, ops), wire_direct=wire_names)
 
     def params_ops(self, accumulate=False, wire=None):
-        """wire: data pointer of the network's bf16 wire buffer - wgrad launches that can write their gradient there directly
-        (GanWgradDesc.dw_wire); self.wire_direct then lists those kernels."""
-        key = ('A', accumulate, wire) if wire else ('A', accumulate)
+        """Pass A (a BwdPlan).  wire: data pointer of the network's bf16 wire buffer - wgrad launches that can write their gradient
+        there directly (GanWgradDesc.dw_wire); the plan's wire_direct lists those kernels."""
+        key = ('A', accumulate, wire or None)
         if key not in self._cache:
             self._cache[key] = self._chain(0, self.N, self.groups, 0, True, False, accumulate, wire=wire)
         return self._cache[key]
 
     def backward_params(self, accumulate=False):
         """Pass A: dlogits (all invocations, written by the loss kernels) -> parameter gradients."""
-        key = ('A', accumulate)
-        if key not in self._cache:
-            self._cache[key] = self._chain(0, self.N, self.groups, 0, True, False, accumulate)
-        self.ctx.run(self._cache[key])      # (the ops carry lane-2/3 workspaces either way)
+        self.ctx.run(self.params_ops(accumulate))      # (the ops carry lane-2/3 workspaces either way)
 
     def backward_input(self, call, dst=None, c0=0):
         """Pass B: gradient w.r.t. the input of invocation `call`; its dlogits must be in self.dlogits_b.
@@ -1452,15 +1468,16 @@ class DiscEvalCall:
         self.a = {'down0': Buf(ctx, B, s1, s1, 64), 'down1': Buf(ctx, B, s2, s2, 128), 'down2': Buf(ctx, B, s3, s3, 256),
                   'conv': Buf(ctx, B, s4, s4, 512)}
         self.logits = Buf(ctx, B, s5, s5, 1, torch.float32)
-        fwd = [bd.conv('conv_fwd', self.xin.view(), self.a['down0'].view(), P.tr['down0.kernel'].data_ptr(), 64, 2, None, 'lrelu',
-                       k_real=net.cin)]
+        conv = lambda *a_, **k_: bd.conv(*a_, **k_)[0]      # (the op alone: a folded layer is finished by its one launch)
+        fwd = [conv('conv_fwd', self.xin.view(), self.a['down0'].view(), P.tr['down0.kernel'].data_ptr(), 64, 2, None, 'lrelu',
+                    k_real=net.cin)]
         prev = 'down0'
         for name, co, stride in DiscCall.LAYERS[1:4]:
-            fwd.append(bd.conv('conv_fwd', self.a[prev].view(), self.a[name].view(), F.nk[name].data_ptr(), co, stride,
-                               F.bias[name].data_ptr(), 'lrelu'))
+            fwd.append(conv('conv_fwd', self.a[prev].view(), self.a[name].view(), F.nk[name].data_ptr(), co, stride,
+                            F.bias[name].data_ptr(), 'lrelu'))
             prev = name
-        fwd.append(bd.conv('conv_fwd', self.a['conv'].view(), self.logits.view(), P.tr['last.kernel'].data_ptr(), 1, 1,
-                           P.ptr('last.bias'), None, 1))
+        fwd.append(conv('conv_fwd', self.a['conv'].view(), self.logits.view(), P.tr['last.kernel'].data_ptr(), 1, 1,
+                        P.ptr('last.bias'), None, 1))
         self.fold_ops = F.fold_ops
         self.fwd_ops = fwd
         self.ops = self.fold_ops + self.fwd_ops

@@ -321,7 +321,7 @@ class Pix2PixStep(_StepBase):
         if self._wgrad_adam_ok():         # (after the warm-up step: G's options are settled)
             adam = (self.b1, self.b2)
             self.g.bwd_stages(list(self.wgrad_cuts), use_dgen2=True, adam=adam)       # (op lists, layer-stack plans, device tables)
-            self.G.params.adam_rest_ops(self.g.adam_fused[(True, False, False, 'own', adam)], self.b1, self.b2)
+            self.G.params.adam_rest_ops(self.g.bwd_plan(use_dgen2=True, adam=adam).adam_fused, self.b1, self.b2)
 
     def ddp_phases(self):
         return [(Phase.GENS, [0]), (Phase.DISCS, [1])]          # (phase, indices into nets() complete after it)
@@ -431,7 +431,7 @@ class Pix2PixStep(_StepBase):
         if not adam_begun:
             self.ctx.run(self.G.params.adam_begin_ops(self.lr, self.b1, self.b2))
         run(adam)
-        self._in_step.wfused = {self.G: self.g.adam_fused[(True, False, False, 'own', adam)]}
+        self._in_step.wfused = {self.G: self.g.bwd_plan(use_dgen2=True, adam=adam).adam_fused}
 
     # ---- data-parallel schedule: bucketed exchange overlapped with the backward pass ---------------------------
     def _capture_bucketed(self):
@@ -462,7 +462,7 @@ class Pix2PixStep(_StepBase):
         stages = g.bwd_stages([8, 12], use_dgen2=True, wire=wG)
         d_params = d.params_ops(wire=wD)
         assert len(stages) == 3
-        skip = {0: set(g.wire_direct[(True, False, False, 'own', None, wG)]) if direct else set(), 1: set(d.wire_direct) if direct else set()}
+        skip = {0: set(g.bwd_plan(use_dgen2=True, wire=wG).wire_direct), 1: set(d_params.wire_direct)}      # (empty without a wire pointer)
         self._wire_direct_names = skip
 
         def pack_bucket(b):
@@ -637,10 +637,10 @@ class CycleGANStep(_StepBase):
 
     def _prebuild_fused_adam(self):
         if self._wgrad_adam_ok() and self.merged and self.two_chains and self.early_adam and self.wide_wgrads and self._wide:
-            adam = (self.b1, self.b2)
+            wide = dict(use_dgen2=True, accumulate=True, wgrads='wide', adam=(self.b1, self.b2))
             for call, net in ((self.gA, self.Gg), (self.gB, self.Gf)):
-                call.bwd_stages([8, 12], use_dgen2=True, accumulate=True, wgrads='wide', adam=adam)
-                net.params.adam_rest_ops(call.adam_fused[(True, False, True, 'wide', adam)], self.b1, self.b2)
+                call.bwd_stages([8, 12], **wide)
+                net.params.adam_rest_ops(call.bwd_plan(**wide).adam_fused, self.b1, self.b2)
 
     def gen_calls(self):
         return dict(fake_y=self.fy, cycled_x=self.cx, fake_x=self.fx, cycled_y=self.cy, same_x=self.sx, same_y=self.sy)
@@ -788,8 +788,8 @@ class CycleGANStep(_StepBase):
                 fused_adam = bool(self._adam_in_chains(mode) and self.early_adam)
 
                 if self._wide is None:       # host and guest must keep down0's output gradient in the same buffer (plan dependent)
-                    self._wide = all(h.bwd_ops(True, False, True, 'wide') is not None and g_.bwd_ops(False, True, False, 'none') is not None
-                                     and h.dy0_in_dA == g_.dy0_in_dA for h, g_ in ((gA, cy), (gB, cx)))
+                    self._wide = all(h.bwd_plan(use_dgen2=True, accumulate=True, wgrads='wide').dy0_in_dA ==
+                                     g_.bwd_plan(need_dx=True, wgrads='none').dy0_in_dA for h, g_ in ((gA, cy), (gB, cx)))
                 wide = self._wide and self.wide_wgrads
                 w1, w2 = ('none', 'wide') if wide else ('own', 'own')
 
@@ -808,11 +808,11 @@ class CycleGANStep(_StepBase):
                         return False
                     P = net.params
                     if wf:
-                        adam = (self.b1, self.b2)
+                        fused = dict(use_dgen2=True, accumulate=True, wgrads='wide', adam=(self.b1, self.b2))
                         self.ctx.run(P.adam_begin_ops(self.lr, self.b1, self.b2))
-                        for ops, wops in gen.bwd_stages([8, 12], use_dgen2=True, accumulate=True, wgrads='wide', adam=adam):
+                        for ops, wops in gen.bwd_stages([8, 12], **fused):
                             self.ctx.run(ops + wops)
-                        self.ctx.run(P.adam_rest_ops(gen.adam_fused[(True, False, True, 'wide', adam)], self.b1, self.b2))
+                        self.ctx.run(P.adam_rest_ops(gen.bwd_plan(**fused).adam_fused, self.b1, self.b2))
                         return True
                     if P._segments is None or len(P._segments) != 3:
                         P.split_kernels_at('down4.kernel', 'up0.kernel')

@@ -571,3 +571,35 @@ def test_full_size_golden_fixtures_are_complete():
         side = (c['S'] + 6) // 7
         key = 'gen_sample' if c['model'] == 'pix2pix' else 'fake_y_sample'
         assert g[key].shape == (c['B'], side, side, 1) and np.abs(g[key]).max() <= 1.0
+
+
+def test_op_records_keep_the_positional_contract():
+    """gan_amd.nets.Op, built with and without meta, under the exact expressions its positional readers apply: bench.py's timed loop
+    (`op[0](*op[1], st)`, `op[2]`, `len(op) > 3 and op[3].get('kind') == 'gemm'`) and tests/launch_audit.py::label_calls (a tuple
+    with a callable first, a tuple second and a string third element).  Always five long; meta is a mapping, never None."""
+    import ctypes as C
+    from gan_amd import _lib as L
+    from gan_amd.nets import Op
+    from tests import launch_audit as A
+    seen = []
+
+    def fn(*a):
+        seen.append(a)
+        return 0
+    t0, t1 = L.GanTensor(None, 0, 0, 0, 0, 0), L.GanTensor(None, 0, 0, 0, 0, 0)
+    bare = Op(fn, (C.byref(t0), 7), "act_bwd")
+    gemm = Op(fn, (C.byref(t1),), "conv_wgrad", dict(kind='gemm', kernel='wgrad<bf16,256,256>', flops=2.0, shape='wgrad A8 B8 M4 s1'), True)
+    for op in (bare, gemm):
+        assert isinstance(op, tuple) and len(op) == 5
+        assert op.meta is not None and op[3] is op.meta and hasattr(op[3], 'get') and isinstance(op[4], bool) and op[4] is op.side
+        assert op[0](*op[1], 123) == 0 and seen[-1] == op[1] + (123,)
+        assert op[2] == op.label
+        assert len(op) >= 3 and callable(op[0]) and isinstance(op[1], tuple) and isinstance(op[2], str)
+    metas = [op[3] if len(op) > 3 and op[3].get('kind') == 'gemm' else None for op in (bare, gemm)]
+    assert metas[0] is None and metas[1]['kernel'] == 'wgrad<bf16,256,256>' and metas[1]['flops'] == 2.0
+    assert len(bare.meta) == 0 and not bare.meta and bare.side is False and gemm.side is True
+    with pytest.raises(TypeError):
+        bare.meta['kind'] = 'gemm'          # the empty meta is shared by every op without one: it must not be writable
+    calls = [A.Call('gan_act_bwd', fn, bare.args), A.Call('gan_conv_wgrad', fn, gemm.args)]
+    A.label_calls(calls, [bare, gemm])
+    assert calls[0].label == 'act_bwd' and calls[1].label == 'conv_wgrad wgrad A8 B8 M4 s1'

@@ -692,7 +692,7 @@ def test_lane_rules_refuse_the_patterns_that_crash_capture_end():
 
 
 def _plans_of(ops):
-    return [o[3]['kernel'] for o in ops if len(o) > 3 and isinstance(o[3], dict)]
+    return [o.meta['kernel'] for o in ops if o.meta]
 
 
 def test_benchmarked_pix2pix_graph_equals_eager_steps():
@@ -719,7 +719,7 @@ def test_benchmarked_pix2pix_graph_equals_eager_steps():
     torch.cuda.synchronize()
     fused = [v for v in st2.g.adam_fused.values() if v]
     assert fused and len(fused[0]) >= 7, st2.g.adam_fused                       # Adam ran inside wgrad launches
-    bwd = [ops for key, ops in st2.g._bwd_cache.items() if len(key) == 5 and key[4] is not None][0]
+    bwd = st2.g.bwd_plan(use_dgen2=True, adam=(st2.b1, st2.b2))
     kernels = set(_plans_of(bwd) + _plans_of(st2.g.fwd_ops) + _plans_of(st2.d.params_ops()))
     assert 'wgrad<bf16,256,256>' in kernels and 'conv_gemm<bf16,1024,64>' in kernels and 'conv_gemm<bf16,256,128>' in kernels, kernels
     assert np.allclose(l_eager, l_graph, rtol=1e-5), (l_eager, l_graph)
@@ -728,6 +728,33 @@ def test_benchmarked_pix2pix_graph_equals_eager_steps():
     got = {k: v for ps in (st2.G.params, st2.D.params) for k, v in ps.state.items()}
     for k, v in s_eager.items():
         assert torch.allclose(v, got[k], rtol=1e-5, atol=1e-7), k
+
+
+def test_wgrad_descriptors_agree_with_the_returned_plans():
+    """Pix2Pix bf16, 256 x 256, batch 1, channels = 1 (the smallest size the 8-level generator takes); op lists are built, no step
+    runs.  G's fused-Adam backward plan, its data-parallel plan with a wire pointer and D's parameter pass with a wire pointer: for
+    every conv_wgrad op the descriptor and the plan that came back with the list agree - adam_fuse is set exactly for the kernels
+    the plan lists as Adam-fused, dw_wire exactly for those it lists as wire-direct (in op order), the list the case is about is
+    not empty, and no kernel is in both."""
+    from gan_amd.nets import Ctx
+    from gan_amd.steps import Pix2PixStep
+    ctx = Ctx('cuda:0', 'bf16')
+    st = Pix2PixStep(ctx, 1, 256, 1)
+    st._settle_gen_options()
+    wire = [torch.zeros(n.params.total, dtype=torch.bfloat16, device=ctx.device) for n in st.nets()]
+    cases = [('G, Adam in the wgrads', st.G, st.g.bwd_plan(use_dgen2=True, adam=(st.b1, st.b2)), 'adam_fused'),
+             ('G, wire pointer', st.G, st.g.bwd_plan(use_dgen2=True, wire=wire[0].data_ptr()), 'wire_direct'),
+             ('D, wire pointer', st.D, st.d.params_ops(wire=wire[1].data_ptr()), 'wire_direct')]
+    for title, net, plan, expected in cases:
+        P = net.params
+        by_grad = {P.ptr(name, 'grad'): name for name in P.nat}
+        descs = [o.args[0]._obj for o in plan if o.label == 'conv_wgrad']
+        assert sorted(by_grad[d.dw] for d in descs) == sorted(P.nat), title          # one wgrad launch per kernel
+        assert [by_grad[d.dw] for d in descs if bool(d.adam_fuse)] == list(plan.adam_fused), title
+        assert [by_grad[d.dw] for d in descs if bool(d.dw_wire)] == list(plan.wire_direct), title
+        assert getattr(plan, expected), title
+        assert not set(plan.adam_fused) & set(plan.wire_direct), title
+        print(f"[{title}] {len(descs)} wgrad launches: Adam-fused {list(plan.adam_fused)}, wire-direct {list(plan.wire_direct)}")
 
 
 def test_benchmarked_cyclegan_graph_equals_eager_steps():

@@ -56,8 +56,7 @@ def cmd_run(a):
             for op in ops:
                 i0 = nlog()
                 run_ops([op], *rest, **kw)
-                meta = op[3] if len(op) > 3 and isinstance(op[3], dict) else None
-                ops_seen.append((i0, nlog(), op[2], meta))
+                ops_seen.append((i0, nlog(), op.label, op.meta or None))
         return f
     ctx.run, ctx.run_on = wrap(ctx.run), wrap(ctx.run_on)
     cap0 = []

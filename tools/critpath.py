@@ -24,7 +24,7 @@ def none(ctx, st): return lambda: None
 def no_gwgrad(ctx, st):
     orig = ctx.run_on
     def run_on(ops, stream):
-        orig([o for o in ops if not (len(o) > 4 and o[4] and o[2] == 'conv_wgrad' and getattr(run_on, 'g', False))], stream)
+        orig([o for o in ops if not (o.side and o.label == 'conv_wgrad' and getattr(run_on, 'g', False))], stream)
     # G's staged wgrads are the only ops run_on() receives with the side flag from GenCall.backward
     import gan_amd.nets as N
     ob = N.GenCall.backward

@@ -39,8 +39,7 @@ def wrap(op, st_handle):
     rc = op[0](*op[1], st_handle)
     e1.record(s)
     assert rc == 0, op[2]
-    meta = op[3] if len(op) > 3 and isinstance(op[3], dict) else None
-    recs.append((lanes.get(st_handle, -1), op[2] + (' ' + meta['shape'] if meta else ''), e0, e1))
+    recs.append((lanes.get(st_handle, -1), op.label + (' ' + op.meta['shape'] if op.meta else ''), e0, e1))
 
 
 def run(ops, lane=0):

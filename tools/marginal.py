@@ -30,8 +30,7 @@ DEFAULT = [
 
 
 def label(op):
-    meta = op[3] if len(op) > 3 and isinstance(op[3], dict) else None
-    return op[2] + (' ' + meta['shape'] + ' ' if meta else '')
+    return op.label + (' ' + op.meta['shape'] + ' ' if op.meta else '')
 
 
 def bench(name, pat, batch):

@@ -21,7 +21,7 @@ def timed(ops, lane=0):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(); rc = op[0](*op[1], st); e1.record()
         assert rc == 0, op[2]
-        recs.append((op[2], op[3] if len(op) > 3 else None, e0, e1))
+        recs.append((op.label, op.meta, e0, e1))
 for _ in range(2):
     step._run(*x, training=True)
 ctx.run = timed
