@@ -205,16 +205,21 @@ class GAN(ABC):
 
     # ---- losses / optimiser (base_gan.py:227-252) ------------------------------------------------
     def loss_object(self):
-        """BinaryCrossentropy(from_logits=True): callable(target_like, logits) -> scalar tensor."""
+        """BinaryCrossentropy(from_logits=True), or with config['gan_loss'] == 'lsgan' the mean squared error on the raw logits
+        (DESIGN.md section 16): callable(target_like, logits) -> scalar tensor."""
         ctx = self.ctx
+        kind = self.config.get('gan_loss', 'bce')
+        if kind not in ('bce', 'lsgan'):
+            raise ValueError(f"gan_loss {kind!r}: 'bce' or 'lsgan'")
+        what = "lsq_logits" if kind == 'lsgan' else "bce_logits"
 
         def bce(y_true, logits):
             t = float(y_true) if np.isscalar(y_true) else float(torch.as_tensor(y_true).flatten()[0])
             x = logits.to(device=ctx.device, dtype=torch.float32).contiguous()
             out = torch.zeros(1, dtype=torch.float32, device=ctx.device)
             ws = torch.empty(1024, dtype=torch.float32, device=ctx.device)
-            L.check(ctx.lib.gan_bce_logits(x.data_ptr(), x.numel(), t, 1.0, 0, out.data_ptr(), 0.0, ctx.dt, None, 8,
-                                           ws.data_ptr(), None, ctx.stream()), "bce_logits")
+            fn = getattr(ctx.lib, "gan_" + what)          # gan_bce_logits / gan_lsq_logits: the same arguments
+            L.check(fn(x.data_ptr(), x.numel(), t, 1.0, 0, out.data_ptr(), 0.0, ctx.dt, None, 8, ws.data_ptr(), None, ctx.stream()), what)
             return out[0]
         return bce
 

@@ -956,3 +956,102 @@ extern "C" int gan_ema_update(float* shadow, const float* param, int64_t count, 
   GAN_CHECK_LAUNCH();
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// least-squares GAN objective (gan_loss 'lsgan')
+// ------------------------------------------------------------------------------------------------
+// bce_kernel's launch with (x - target)^2 in place of the cross-entropy term: same buffers, pitch, partial sums and finalize
+// (l1_finalize_kernel).  Logits are unbounded under this loss: there is no exp and nothing saturates, a large |x| gives a
+// large term and a large gradient (in f16 one beyond 65,504 is stored as inf, which the loss scale's check then sees).
+template <typename T>
+__global__ __launch_bounds__(256) void lsq_kernel(const float* x, long long count, float target, float grad_scale, T* dx,
+                                                  int dx_pitch, float* partial, const float* ls) {
+  if (ls) grad_scale *= ls[0];          // dynamic loss scale (fp16 path): gradients only, the reported loss is unscaled
+  __shared__ float red[4];
+  float s = 0.f;
+  const float g2 = 2.0f * grad_scale;   // (exact)
+  const float inv = 1.0f / (float)count;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+    const float d = x[i] - target;
+    s += d * d;
+    if (dx) st_f(dx + i * dx_pitch, (g2 * d) * inv);
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// The three least-squares terms of one Pix2Pix step in one pass, in patchgan_bce_kernel's layout: partial[blocks][3] = sums of
+// (f-1)^2, (r-1)^2, f^2 -> patchgan_finalize_kernel, unchanged (gan = [0], disc = 0.5 * [1] + 0.5 * [2], gen_total).
+template <typename T>
+__global__ __launch_bounds__(256) void patchgan_lsq_kernel(const float* real, const float* fake, long long count,
+                                                           T* g_dfake, T* d_dreal, T* d_dfake, int pitch, float* partial,
+                                                           const float* ls) {
+  __shared__ float red[4][3];
+  float s[3] = {0.f, 0.f, 0.f};
+  const float inv = (ls ? ls[0] : 1.0f) / (float)count;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
+    const float r = real[i], f = fake[i];
+    const float df = f - 1.f, dr = r - 1.f;
+    s[0] += df * df;                                // (fake - 1)^2
+    s[1] += dr * dr;                                // (real - 1)^2
+    s[2] += f * f;                                  // fake^2
+    if (g_dfake) st_f(g_dfake + i * pitch, (2.f * df) * inv);
+    if (d_dreal) st_f(d_dreal + i * pitch, dr * inv);         // 0.5 * 2 (r - 1)
+    if (d_dfake) st_f(d_dfake + i * pitch, f * inv);          // 0.5 * 2 f
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float w = wave_sum(s[k]);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) partial[blockIdx.x * 3 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+extern "C" {
+
+int gan_lsq_logits(const float* x, int64_t count, float target, float loss_scale, int32_t loss_accumulate,
+                   float* loss_out, float grad_scale, int32_t dtype, void* dx, int32_t dx_pitch, float* workspace,
+                   const float* scale_state, gan_stream_t stream) {
+  if (!x || !loss_out || !workspace || count <= 0) return GAN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  int blocks = (int)((count + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  int rc = with_dtype(dtype, [&](auto* tag) {
+    typedef GAN_TAG_T(tag) T;
+    GAN_LAUNCH(lsq_kernel<T>, dim3(blocks), dim3(256), 0, st, x, (long long)count, target, grad_scale, (T*)dx, dx_pitch,
+                       workspace, scale_state);
+    GAN_CHECK_LAUNCH();
+    return 0;
+  });
+  if (rc) return rc;
+  GAN_LAUNCH(l1_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, blocks, 1.0 / (double)count,
+                     loss_scale, loss_accumulate, loss_out);
+  GAN_CHECK_LAUNCH();
+  return 0;
+}
+
+int gan_patchgan_losses_lsq(const float* real_logits, const float* fake_logits, int64_t count, int32_t dtype, void* g_dfake,
+                            void* d_dreal, void* d_dfake, int32_t pitch, float lambda, const float* l1, float* gen_total,
+                            float* gan_loss, float* disc_loss, float* workspace, const float* scale_state, gan_stream_t stream) {
+  if (!real_logits || !fake_logits || count <= 0 || !gan_loss || !disc_loss || !workspace) return GAN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  int blocks = (int)((count + 255) / 256);
+  if (blocks > 256) blocks = 256;
+  int rc = with_dtype(dtype, [&](auto* tag) {
+    typedef GAN_TAG_T(tag) T;
+    GAN_LAUNCH(patchgan_lsq_kernel<T>, dim3(blocks), dim3(256), 0, st, real_logits, fake_logits, (long long)count,
+                       (T*)g_dfake, (T*)d_dreal, (T*)d_dfake, pitch, workspace, scale_state);
+    GAN_CHECK_LAUNCH();
+    return 0;
+  });
+  if (rc) return rc;
+  GAN_LAUNCH(patchgan_finalize_kernel, dim3(1), dim3(64), 0, st, (const float*)workspace, blocks, 1.0 / (double)count, lambda,
+                     l1, gen_total, gan_loss, disc_loss);
+  GAN_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // extern "C"

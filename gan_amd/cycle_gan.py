@@ -124,7 +124,8 @@ class CycleGAN(GAN):
         if key not in self._steps:
             st = CycleGANStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
                               lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
-                              seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=tuple(m.net for m in self._models()))
+                              seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=tuple(m.net for m in self._models()),
+                              gan_loss=self.config.get('gan_loss', 'bce'))
             st.sync = self.sync
             if training and self.generator_g_ema is not None:
                 st.ema = (self.generator_g_ema, self.generator_f_ema)
@@ -227,6 +228,9 @@ def parse_opt(argv=None):
     parser.add_argument('--beta-2', type=float, default=0.999, help='exponential decay rate for 2st moment of Adam optimizer for generators and discriminators')
     parser.add_argument('--weights', type=str, help='path to pretrained model weights for prediction', required='--predict' in argv)
     parser.add_argument('--dtype', type=str, default='bf16', choices=['bf16', 'f16', 'f32'])
+    parser.add_argument('--gan-loss', type=str, default='bce', choices=['bce', 'lsgan'],
+                        help="adversarial loss on the discriminators' logits: 'bce' = sigmoid cross-entropy (the reference); "
+                             "'lsgan' = least squares, mean((logit - target)^2), the objective of the CycleGAN paper")
     parser.add_argument('--predict-training', type=str, default='true', choices=['true', 'false'],
                         help="--predict only: 'true' = the reference's generator(x, training=True) at batch 1 (batch statistics, "
                              "dropout); 'false' = Keras inference mode (moving statistics, no dropout) in batches of --batch-size")

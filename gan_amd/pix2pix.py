@@ -143,7 +143,7 @@ class Pix2Pix(GAN):
             st = Pix2PixStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
                              lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
                              seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net),
-                             generator_loss=self.config.get('generator_loss', 'l1'))
+                             generator_loss=self.config.get('generator_loss', 'l1'), gan_loss=self.config.get('gan_loss', 'bce'))
             st.sync = self.sync
             if training and self.generator_ema is not None:
                 st.ema = (self.generator_ema,)
@@ -322,6 +322,9 @@ def parse_opt(argv=None):
     parser.add_argument('--generator-loss', type=str, default='l1', choices=['l1', 'ssim', 'dssim'],
                         help="secondary generator loss: 'l1' = mean |target - generated|; 'dssim' = 1 - mean SSIM(generated, target), computed "
                              "with its gradient on the GPU; 'ssim' (the reference's input-against-target term) is refused")
+    parser.add_argument('--gan-loss', type=str, default='bce', choices=['bce', 'lsgan'],
+                        help="adversarial loss on the discriminator's logits: 'bce' = sigmoid cross-entropy (the reference); "
+                             "'lsgan' = least squares, mean((logit - target)^2)")
     parser.add_argument('--input-img-orient', type=str, default='left', choices=['left', 'right'], help='whether input image is on left (i.e. target right) or vice-versa')
     parser.add_argument('--seed', type=int, default=123, help='seed value for random number generator')
     group = parser.add_mutually_exclusive_group(required=True)

@@ -65,7 +65,10 @@ class _InStepAdam:
 class _StepBase:
     ddp_buckets = False          # data parallel: a step type with a bucketed schedule (_capture_bucketed) turns it on
 
-    def __init__(self, ctx: Ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses):
+    def __init__(self, ctx: Ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses, gan_loss='bce'):
+        if gan_loss not in ('bce', 'lsgan'):
+            raise ValueError(f"gan_loss {gan_loss!r}: 'bce' or 'lsgan'")
+        self.gan_loss = gan_loss     # the adversarial term: sigmoid cross-entropy, or least squares on the raw logits
         self.ctx, self.B, self.S, self.C = ctx, batch, size, channels
         self.lam, self.lr, self.b1, self.b2 = float(lam), lr, beta_1, beta_2
         self.losses = torch.zeros(n_losses, dtype=torch.float32, device=ctx.device)
@@ -80,10 +83,12 @@ class _StepBase:
         return [torch.zeros(sh, dtype=torch.float32, device=self.ctx.device) for _ in range(2)]
 
     def _bce(self, logits_ptr, count, target, loss_idx, loss_scale, acc, grad_scale, dx_ptr, ws=None):
+        """One adversarial term against a constant target: gan_bce_logits, or (gan_loss 'lsgan') gan_lsq_logits - same arguments."""
         lib, ctx = self.ctx.lib, self.ctx
-        rc = lib.gan_bce_logits(logits_ptr, count, target, loss_scale, int(acc), self.losses.data_ptr() + 4 * loss_idx,
-                                grad_scale, ctx.dt, dx_ptr, 8, (ws if ws is not None else self.bce_ws).data_ptr(), ctx.ls_ptr, ctx.stream())
-        L.check(rc, "bce_logits")
+        fn, what = (lib.gan_lsq_logits, "lsq_logits") if self.gan_loss == 'lsgan' else (lib.gan_bce_logits, "bce_logits")
+        rc = fn(logits_ptr, count, target, loss_scale, int(acc), self.losses.data_ptr() + 4 * loss_idx,
+                grad_scale, ctx.dt, dx_ptr, 8, (ws if ws is not None else self.bce_ws).data_ptr(), ctx.ls_ptr, ctx.stream())
+        L.check(rc, what)
 
     def _l1(self, a, b, loss_idx, loss_scale, acc, grad_scale, da, stream=None, ws=None):
         lib, ctx = self.ctx.lib, self.ctx
@@ -281,10 +286,10 @@ class Pix2PixStep(_StepBase):
     ddp_wire_direct = True       # bf16 all-reduce exchange: wgrad launches write their gradients straight into the wire buffer
 
     def __init__(self, ctx: Ctx, batch, size, channels=1, lam=100.0, lr=2e-4, beta_1=0.5, beta_2=0.999,
-                 seed=123, dropout=True, nets=None, mask_stream=0, generator_loss='l1'):
+                 seed=123, dropout=True, nets=None, mask_stream=0, generator_loss='l1', gan_loss='bce'):
         if generator_loss not in ('l1', 'dssim'):
             raise ValueError(f"generator_loss {generator_loss!r}: 'l1' or 'dssim'")
-        super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=8)
+        super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=8, gan_loss=gan_loss)
         self.generator_loss = generator_loss       # the secondary term (losses[2]): mean |target - gen|, or 1 - mean SSIM
         if generator_loss == 'dssim':
             need = ctx.lib.gan_dssim_workspace_bytes(batch, size, size, channels)
@@ -380,9 +385,10 @@ class Pix2PixStep(_StepBase):
         real_ptr, cnt = d.logits_view(0)
         fake_ptr, _ = d.logits_view(1)
         lp = self.losses.data_ptr()
-        L.check(ctx.lib.gan_patchgan_losses(real_ptr, fake_ptr, cnt, ctx.dt, d.dlogits_b.t.data_ptr(), d.dlogits_ptr(0),
-                                            d.dlogits_ptr(1), 8, self.lam, lp + 8, lp, lp + 4, lp + 12,
-                                            self.bce_ws.data_ptr(), ctx.ls_ptr, ctx.stream()), "patchgan_losses")
+        three = ctx.lib.gan_patchgan_losses_lsq if self.gan_loss == 'lsgan' else ctx.lib.gan_patchgan_losses      # (same arguments)
+        L.check(three(real_ptr, fake_ptr, cnt, ctx.dt, d.dlogits_b.t.data_ptr(), d.dlogits_ptr(0),
+                      d.dlogits_ptr(1), 8, self.lam, lp + 8, lp, lp + 4, lp + 12,
+                      self.bce_ws.data_ptr(), ctx.ls_ptr, ctx.stream()), "patchgan_losses")
 
     def _backward(self, phase, mode, adam_begun):
         """Two independent chains: D's parameter gradients (pix2pix.py:211) beside G's backward (:210)."""
@@ -584,8 +590,8 @@ class CycleGANStep(_StepBase):
     wide_wgrads = True           # ... one wgrad GEMM per layer over a generator's three invocations (host + guest call)
 
     def __init__(self, ctx: Ctx, batch, size, channels=1, lam=10.0, lr=2e-4, beta_1=0.5, beta_2=0.999,
-                 seed=123, dropout=True, nets=None, mask_stream=0, merged=True):
-        super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=12)     # [0..8] as below; [9] cycle term of chain B; [10] stays 0
+                 seed=123, dropout=True, nets=None, mask_stream=0, merged=True, gan_loss='bce'):
+        super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=12, gan_loss=gan_loss)     # [0..8] as below; [9] cycle term of chain B; [10] stays 0
         n = 'instancenorm'                                                    # cycle_gan.py:30-33
         if nets is not None:
             self.Gg, self.Gf, self.Dx, self.Dy = nets

@@ -365,6 +365,21 @@ int gan_bce_logits(const float* x, int64_t count, float target, float loss_scale
 int gan_patchgan_losses(const float* real_logits, const float* fake_logits, int64_t count, int32_t dtype, void* g_dfake,
                         void* d_dreal, void* d_dfake, int32_t pitch, float lambda, const float* l1, float* gen_total,
                         float* gan_loss, float* disc_loss, float* workspace, const float* scale_state, gan_stream_t stream);
+/* Least-squares GAN objective (gan_loss 'lsgan'): the arguments of gan_bce_logits, one for one.
+ * x: fp32 logits [count] (unbounded). loss_out[0] (+)= loss_scale * mean((x-target)^2). If dx != NULL:
+ * dx[i*dx_pitch] = grad_scale * ls * 2*(x[i]-target)/count in `dtype`, ls = scale_state[0] or 1.  workspace >= 1024
+ * floats (block partial sums, added in a fixed order by a finalize launch). */
+int gan_lsq_logits(const float* x, int64_t count, float target, float loss_scale, int32_t loss_accumulate,
+                   float* loss_out, float grad_scale, int32_t dtype, void* dx, int32_t dx_pitch, float* workspace,
+                   const float* scale_state, gan_stream_t stream);
+/* The three least-squares terms of one Pix2Pix / PatchGAN step in one pass; the arguments of gan_patchgan_losses, one
+ * for one: gan_loss = mean((fake-1)^2), disc_loss = 0.5*(mean((real-1)^2) + mean(fake^2)), gradients (optional,
+ * `dtype`, element stride `pitch`, each times ls): g_dfake = 2(fake-1)/count, d_dreal = (real-1)/count,
+ * d_dfake = fake/count.  If gen_total != NULL it receives gan_loss + lambda * (*l1), two roundings.
+ * workspace >= 768 floats. */
+int gan_patchgan_losses_lsq(const float* real_logits, const float* fake_logits, int64_t count, int32_t dtype, void* g_dfake,
+                            void* d_dreal, void* d_dfake, int32_t pitch, float lambda, const float* l1, float* gen_total,
+                            float* gan_loss, float* disc_loss, float* workspace, const float* scale_state, gan_stream_t stream);
 /* tf.reduce_mean(tf.abs(a - b)) (pix2pix.py:181, cycle_gan.py:167,176). loss_out (+)= loss_scale*mean.
  * da (optional, dtype, own pitch) = grad_scale * sign(a-b)/count. workspace >= 4096 floats. */
 int gan_l1(int32_t dtype, const GanTensor* a, const GanTensor* b, float loss_scale, int32_t loss_accumulate,
