@@ -1,5 +1,5 @@
-"""Launch audit of a captured training step and of the inference forward (helper of tests/test_gpu_launch_audit.py and
-tests/test_gpu_eval_audit.py; not a conftest).
+"""Launch audit of a captured training step and of the inference forward (helper of tests/test_gpu_launch_audit.py,
+tests/test_gpu_wide_audit.py and tests/test_gpu_eval_audit.py; not a conftest).
 
 record(): every library call the step's capture body makes (Ctx.capture_graph's fn: the eager warm-up step is left out), or an
 eager call makes inside Recorder.recording() (the inference calls: nothing of them is captured), with the descriptors the product
@@ -19,7 +19,11 @@ Adam graphs' calls; replay(check=...) leaves the calls the one-GPU audit already
 RGB steps (tests/test_gpu_rgb_audit.py, channels = 3): thin_call() is the predicate of the calls that differ from the channels = 1
 step (an operand with <= 8 channels), conv_class() / wgrad_class() the plan class of a descriptor as the host tables of
 tests/test_cpu_launch_audit.py key it, missing_required() names the required calls no checked row holds, pad_channels() the
-image-side buffers whose padding channels are not bit-zero."""
+image-side buffers whose padding channels are not bit-zero.
+
+Wide sweeps (tests/test_gpu_wide_audit.py): captured_step() is the body it shares with tests/test_gpu_launch_audit.py (build, capture,
+reset_step, lattice inputs), outside_classes() the predicate of the calls whose plan class no earlier case has audited,
+missing_classes() names the classes a case was added for that none of its checked rows holds."""
 from __future__ import annotations
 
 import contextlib
@@ -998,6 +1002,27 @@ def call_class(call):
     return None
 
 
+def outside_classes(audited):
+    """Predicate of replay(check=...): a recorded conv / wgrad call whose plan class (call_class) is not in `audited` - the calls
+    a class audit of tests/test_gpu_wide_audit.py checks.  Every other entry point is issued unchecked."""
+    def check(call):
+        k = call_class(call)
+        return k is not None and k not in audited
+    return check
+
+
+def missing_classes(calls, rows, required):
+    """required: {class: tag of a launch the host table files under it}.  The classes no CHECKED row holds (in the manner of
+    missing_required), each with what the case recorded of it."""
+    held = {}
+    for c, r in zip(calls, rows):
+        k = call_class(c)
+        if k is not None:
+            held.setdefault(k, []).append(r[4] is not None)
+    return [f"{tag} {k}: " + (f"{len(held[k])} call(s) recorded, none checked" if k in held else "no call of this class recorded")
+            for k, tag in required.items() if not any(held.get(k, ()))]
+
+
 def thin_call(call):
     """Does the call have an operand of <= THIN_C channels?  These are the calls whose code path depends on the image's channel
     count: conv ops by x.c, y.c or w_rows, wgrad by big_c or small_c, gan_bias_grad / gan_act_bwd by the tensor they reduce / write."""
@@ -1258,6 +1283,64 @@ def _short(sym):
         return sym
     n = int(m.group(1))
     return sym[m.end():m.end() + n]
+
+
+# ---- the captured one-GPU step at channels = 1: what tests/test_gpu_launch_audit.py and tests/test_gpu_wide_audit.py replay ----------
+def reset_step(step, saved):
+    for net, (P, state) in zip(step.nets(), saved):
+        ps = net.params
+        ps.master.copy_(P)
+        ps.prepare()
+        # non-zero moments: the fused-Adam checks then see the carried beta * m_old / beta2 * v_old terms too, and the blocks a
+        # launch may skip where the gradient is zero (wgrad.dead_taps) must still apply them
+        g = torch.Generator(device='cpu').manual_seed(11)
+        ps.m.copy_(1e-4 * torch.randn(ps.m.shape, generator=g))
+        ps.v.copy_(1e-8 * torch.rand(ps.v.shape, generator=g) + 1e-10)
+        ps.step.zero_(); ps.grad.zero_()
+        for k, t in ps.state.items():
+            t.copy_(state[k])
+
+
+def captured_step(model, dtype, size, batch, monkeypatch):
+    """Build the step, capture it as bench.py does with every library call of the capture body recorded, then put it at the known
+    start: initial weights, step 0, small random moments (reset_step), inputs on the normalize() lattice (base_gan.py:56-61).
+    -> (step, labelled calls, the captured replay: the caller keeps it alive while it re-issues the calls)."""
+    import gc
+    from gan_amd.nets import Ctx, workspace_mb_for
+    from gan_amd.steps import CycleGANStep, Pix2PixStep
+    # the graphs and events of the previous case must be gone before this one captures: destroying them inside a capture (a cyclic
+    # garbage collection run at an allocation) aborts the process
+    gc.collect()
+    torch.cuda.synchronize()
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    rec = Recorder(monkeypatch)                   # before the step object: its op lists hold the bound entry points
+    rec.hook_capture(monkeypatch)
+    ctx = Ctx('cuda:0', dtype, workspace_mb=workspace_mb_for(batch, size))
+    if model == 'pix2pix':
+        st = Pix2PixStep(ctx, batch, size, 1, lam=100.0, seed=123)
+    else:
+        st = CycleGANStep(ctx, batch, size, 1, lam=10.0, seed=123)
+    saved = [(n.params.master.clone(), {k: t.clone() for k, t in n.params.state.items()}) for n in st.nets()]
+    replay_ = st.capture(training=True)           # what bench.py captures
+    torch.cuda.synchronize()
+    calls = rec.calls
+    assert calls, "nothing recorded inside the capture body"
+    label_calls(calls, st)
+    reset_step(st, saved)
+    g = torch.Generator().manual_seed(7 + batch)
+    for t in replay_.inputs:
+        t.copy_((torch.randint(0, 256, tuple(t.shape), generator=g).float() / 127.5 - 1.0).to(t.device))
+    torch.cuda.synchronize()
+    return st, calls, replay_
+
+
+def report(title, rows, t0, t1, t2):
+    """Print the table, the worst error / gate per entry point and the times of one case."""
+    print('\n' + table(rows, title))
+    worst = worst_per_entry(rows)
+    print(f"[{title}] worst error/gate per entry point: " + ', '.join(f"{k[4:]} {v:.3f}" for k, v in sorted(worst.items())))
+    print(f"[{title}] {len(rows)} calls ({sum(r[4] is not None for r in rows)} checked); "
+          f"build + capture {t1 - t0:.1f} s, audit {t2 - t1:.1f} s")
 
 
 AS_ONE_GPU = 'as in the one-GPU step'

@@ -1,10 +1,14 @@
-"""CPU side of the launch audit (tests/launch_audit.py, tests/test_gpu_launch_audit.py):
+"""CPU side of the launch audit (tests/launch_audit.py, tests/test_gpu_launch_audit.py, tests/test_gpu_wide_audit.py):
   - the audit's fp64 references of the four conv entry points and of wgrad, decoded from the device weight layout, against the
     oracle's Keras-layout convolutions;
   - plan coverage: the plan class of every convolution / wgrad launch in the table of plan_classes() (the captured one-GPU Pix2Pix
     and CycleGAN steps at channels = 1, see there) at B = 1..16 (256x256) and B = 1..8 (512x512, BASELINE config 4's per-GPU batch),
     from the host-side planners, must be reached by a batch the GPU audit runs.  A planner change that creates a class no audited
     batch reaches fails here and names the batch sizes that reach it;
+  - the wide sweeps (tests/test_gpu_wide_audit.py): the classes keyed by (dtype family, class) - 16-bit and fp32 - over Pix2Pix and
+    CycleGAN at B = 1..64 / 1..32 (256x256) and 1..16 (512x512) at 16-bit storage, 1..16 / 1..8 at fp32, from tables that file a
+    launch which finishes its layer under its own class and hold the captured schedule's discriminator forward alone; every class
+    must be reached by a case of tests/test_gpu_launch_audit.py of the same family or by one of WIDE_FULL / WIDE_CLASS;
   - the same for the inference forward (eval_plan_classes(): the BatchNorm generator and PatchGAN in eval mode, every BatchNorm
     layer one convolution with bias + activation; tests/test_gpu_eval_audit.py) at B = 1..64 (256x256) and B = 1..16 (512x512);
   - the gate of check_conv and the bit-equality of check_fold must be able to fail: a float32 model of convolution + bias +
@@ -96,10 +100,19 @@ def IMG(n, h, c):
     return L.GanTensor(16, n, h, h, c, 8)
 
 
-def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None, channels=1, thin=None):
+def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None, channels=1, thin=None, fused=False, captured=False):
     """{class: label} of every conv / wgrad launch of one captured step at `channels` image channels (1: the steps of
     tests/test_gpu_launch_audit.py; 3: tests/test_gpu_rgb_audit.py).  thin: a set that receives the classes of the launches with an
     operand of <= 8 channels (launch_audit.THIN_C: the launches whose code path depends on `channels`).
+    fused: the GanNormFuse requests are complete (an output tensor, and in the forward form gamma / beta / mean / rstd, as
+    nets._Builder.fwd_norm_fuse / bwd_norm_fuse fill them), so the planner honours them where the step's launches have them honoured
+    and the class of such a launch reads 'full', as launch_audit.call_class reads it from a recorded descriptor.  Off (the tables
+    before the wide sweeps): the request is an empty struct, which the planner never honours - such a launch is filed under the class
+    it would have with its own statistics epilogue, and a recorded 'full' class is in no table.
+    captured: only the discriminator forward of the captured schedule (Pix2Pix: per invocation, B images; CycleGAN: D(real) ++ D(fake)
+    as one forward over 2B).  Off: both forms, of which a captured step launches one - the other's classes are then in the table of a
+    batch whose step does not launch them.  With fused and captured the table holds exactly the classes the captured step launches
+    (tests/test_gpu_wide_audit.py asserts it for every case it builds).
     ddp: None - the one-GPU step; 'direct' - the data-parallel Pix2Pix step on its bucketed schedule with the bf16 wire
     (Pix2PixStep._capture_bucketed): every wgrad launch is given its place in the wire buffer and writes it where
     gan_wgrad_wire_direct says it can; 'plain' - every other data-parallel schedule (fp32 wire, ddp_wire_direct = False, the phased
@@ -131,6 +144,11 @@ def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None, channels=1, thi
                 groups = 0                           # activation-only backward: no statistics partials
             if skip:
                 bf.add = L.GanTensor(16, y.n, y.h, y.w, cols, cols)
+        if fused and nf is not None:
+            oc = bwd[0] if bwd is not None else y.c
+            nf.out = L.GanTensor(16, y.n, y.h, y.w, oc, oc)
+            if bwd is None:
+                nf.gamma = nf.beta = nf.mean = nf.rstd = 16
         d = L.GanConvDesc(dt, stride, x, y, 16, w_rows or y.c, 16 if bias else None, act, 0.3, y_f32, 16, 1 << 40,
                           16 if groups else None, groups, 1 << 30, C.addressof(bf) if bf is not None else None,
                           C.addressof(nf) if nf is not None else None)
@@ -229,8 +247,10 @@ def plan_classes(model, B, S, dt=L.BF16, ddp=None, strings=None, channels=1, thi
             generator(B, True)
             generator_wgrads(3 * B, 2)
         d_conc = 2
-    disc_forward(B, 1)
-    disc_forward(2 * B, 2)
+    if not captured or model == 'pix2pix':
+        disc_forward(B, 1)
+    if not captured or model == 'cyclegan':
+        disc_forward(2 * B, 2)
     disc_chain(2 * B, 2, True, d_conc)
     disc_chain(B, 1, False, d_conc)
     return out
@@ -252,6 +272,137 @@ def test_audited_batches_reach_every_plan_class():
             if cls not in audited:
                 missing.append(f"{model} {S}x{S}: class {cls} ({where[0][1]}) reached at B = {[b for b, _ in where]}, audited {AUDITED[key]}")
     assert not missing, "plan classes no audited batch reaches:\n" + "\n".join(missing)
+
+
+# ---- wide sweeps: fp32, CycleGAN 512x512 and the batches above SWEEP (tests/test_gpu_wide_audit.py) ---------------------------------
+# SWEEP above is 16-bit storage only and ends at the batches of BASELINE's configurations.  The command lines accept any
+# --batch-size (the inference sweep already goes to 64 / 16), BASELINE config 5 is CycleGAN at 512x512, and fp32 - the exact-MFMA
+# path every oracle-parity gate rests on - had one audited case.  conv_class() carries no dtype, so a class is keyed here by
+# (dtype family, class): the planner tells 16-bit storage from fp32 and nothing else (asserted below for F16 / BF16 over the whole
+# 16-bit sweeps).  A family's classes are pooled over models and sizes: a class is a kernel, tile, split and epilogue form, whichever
+# network launches it.  The tables are plan_classes(fused=True, captured=True): a launch that finishes its layer (GanNormFuse
+# honoured) has a class of its own ('full'), as launch_audit.call_class gives a recorded one, and the discriminator forward is the
+# captured schedule's alone, so a batch is not credited with a class its step never launches.
+FAMILY = {'bf16': '16-bit', 'f16': '16-bit', 'f32': 'fp32'}
+DTYPE = {'bf16': L.BF16, 'f16': L.F16, 'f32': L.F32}
+WIDE_SWEEP = {
+    '16-bit': {('pix2pix', 256): range(1, 65), ('cyclegan', 256): range(1, 33), ('pix2pix', 512): range(1, 17), ('cyclegan', 512): range(1, 17)},
+    'fp32': {('pix2pix', 256): range(1, 17), ('cyclegan', 256): range(1, 17), ('pix2pix', 512): range(1, 9), ('cyclegan', 512): range(1, 9)},
+}
+# tests/test_gpu_wide_audit.py's cases, in the order it runs them.  WIDE_FULL: every launch checked (the cheapest CycleGAN shape: the
+# f16 loss-scaled InstanceNorm chain, the fp32 CycleGAN launches).  WIDE_CLASS: (model, dtype, size) -> batches whose launches of a
+# class no earlier case of the family has audited are checked; earlier = tests/test_gpu_launch_audit.py::AUDIT_CASES, WIDE_FULL and
+# the entries before it here.  Per key the smallest set that covers, the smaller of two batches that reach the same classes.
+WIDE_FULL = (('cyclegan', 'f16', 256, 1), ('cyclegan', 'f32', 256, 1))
+WIDE_CLASS = {
+    ('pix2pix', 'f32', 256): (3, 5),
+    ('pix2pix', 'f32', 512): (5,),
+    ('cyclegan', 'f32', 256): (9,),
+    ('cyclegan', 'f32', 512): (5, 7),
+    ('pix2pix', 'bf16', 256): (49,),
+    ('cyclegan', 'bf16', 256): (25,),
+    ('cyclegan', 'bf16', 512): (9,),
+}
+_WIDE = {}
+
+
+def wide_classes(model, dtype, S, B):
+    """{class: tag} of one step in the wide tables (same_class keys, as a recorded call has them)."""
+    key = (model, dtype, S, B)
+    if key not in _WIDE:
+        _WIDE[key] = {A.same_class(k): tag for k, tag in plan_classes(model, B, S, DTYPE[dtype], fused=True, captured=True).items()}
+    return _WIDE[key]
+
+
+def wide_earlier():
+    """The cases that ran before WIDE_CLASS: (model, dtype, size, batch) of the one-GPU audit and the full audits."""
+    from tests.test_gpu_launch_audit import AUDIT_CASES
+    return list(AUDIT_CASES) + list(WIDE_FULL)
+
+
+def wide_class_cases(table=None):
+    return [(m, d, s, b) for (m, d, s), bs in (WIDE_CLASS if table is None else table).items() for b in bs]
+
+
+def wide_audited(cases, family):
+    """The classes of a dtype family that the cases' steps launch."""
+    out = set()
+    for m, d, s, b in cases:
+        if FAMILY[d] == family:
+            out |= set(wide_classes(m, d, s, b))
+    return out
+
+
+def wide_new_classes(case, table=None):
+    """{class: tag}: the classes `case` (one of wide_class_cases) is the first of its family to audit - what it was added for."""
+    cases = wide_class_cases(table)
+    before = wide_audited(wide_earlier() + cases[:cases.index(case)], FAMILY[case[1]])
+    m, d, s, b = case
+    return {k: tag for k, tag in wide_classes(m, d, s, b).items() if k not in before}
+
+
+def wide_reach(family):
+    """{class: [(model, size, batch, tag)]} over the family's wide sweep."""
+    dtype = 'f32' if family == 'fp32' else 'bf16'
+    reach = {}
+    for (m, s), batches in WIDE_SWEEP[family].items():
+        for B in batches:
+            for cls, tag in wide_classes(m, dtype, s, B).items():
+                reach.setdefault(cls, []).append((m, s, B, tag))
+    return reach
+
+
+def wide_missing(table=None):
+    missing = []
+    cases = wide_earlier() + wide_class_cases(table)
+    for family in WIDE_SWEEP:
+        seen = wide_audited(cases, family)
+        for cls, where in wide_reach(family).items():
+            if cls not in seen:
+                at = {}
+                for m, s, B, tag in where:
+                    at.setdefault(f"{m} {s}x{s}", []).append(B)
+                missing.append(f"{family} class {cls} ({where[0][3]}) reached at " + ', '.join(f"{k} B = {v}" for k, v in at.items()))
+    return missing
+
+
+@pytest.mark.skipif(not HAVE_LIB, reason="library not built")
+def test_f16_and_bf16_plan_alike_over_the_wide_sweeps():
+    """One 16-bit dtype per case suffices: the class sets are equal at every point of the 16-bit sweeps, CycleGAN included."""
+    for (m, s), batches in WIDE_SWEEP['16-bit'].items():
+        for B in batches:
+            assert set(wide_classes(m, 'f16', s, B)) == set(wide_classes(m, 'bf16', s, B)), (m, s, B)
+            assert set(plan_classes(m, B, s, L.F16)) == set(plan_classes(m, B, s, L.BF16)), (m, s, B)
+
+
+@pytest.mark.skipif(not HAVE_LIB, reason="library not built")
+def test_wide_cases_reach_every_plan_class_of_the_wide_sweeps():
+    for family, sweep in WIDE_SWEEP.items():
+        reach = wide_reach(family)
+        old = wide_audited(wide_earlier()[:-len(WIDE_FULL)], family)
+        print(f"{family}: {len(reach)} classes, {len(set(reach) - old)} of them launched by no case of tests/test_gpu_launch_audit.py")
+        for (m, s), batches in sweep.items():
+            own = {c for c, where in reach.items() if any(w[:2] == (m, s) for w in where)}
+            print(f"  {m} {s}x{s} B = {batches[0]}..{batches[-1]}: {len(own)} classes, {len(own - old)} not launched")
+    missing = wide_missing()
+    assert not missing, "plan classes of the wide sweeps that no audit case reaches:\n" + "\n".join(missing)
+    # the wide sweeps contain the narrow one, and every case lies inside its sweep
+    for (m, s), batches in SWEEP.items():
+        assert set(batches) <= set(WIDE_SWEEP['16-bit'][(m, s)])
+    for m, d, s, b in wide_class_cases() + list(WIDE_FULL):
+        assert b in WIDE_SWEEP[FAMILY[d]][(m, s)], (m, d, s, b)
+    for case in wide_class_cases():
+        new = wide_new_classes(case)
+        print(f"  {case}: added for {sorted(new.items(), key=str)}")
+        assert new, f"{case} audits no class that an earlier case has not audited"
+    # the test can fail: without the largest batch of a key a class is left out, and the message names the batches that reach it
+    for key, batches in WIDE_CLASS.items():
+        less = wide_missing({**WIDE_CLASS, key: batches[:-1]})
+        assert less and all(f"{FAMILY[key[1]]} class" in msg and f"{key[0]} {key[2]}x{key[2]} B = " in msg for msg in less), (key, less)
+        assert all(batches[-1] in [int(v) for v in msg.split(f"{key[0]} {key[2]}x{key[2]} B = [")[1].split(']')[0].split(',')] for msg in less), (key, less)
+        # and no smaller batch of that key does what its largest one does
+        for b in range(WIDE_SWEEP[FAMILY[key[1]]][key[0], key[2]][0], batches[-1]):
+            assert wide_missing({**WIDE_CLASS, key: batches[:-1] + (b,)}), (key, b)
 
 
 # ---- plan coverage of the inference forward ------------------------------------------------------------------------------------
