@@ -136,6 +136,11 @@ class GanTileBlendDesc(_Desc):
                 ("accumulate", C.c_int32)]
 
 
+class GanLrSchedule(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("lr", C.c_float), ("end_factor", C.c_float), ("decay_start", C.c_int32),
+                ("decay_end", C.c_int32)]
+
+
 # name -> (restype, argtypes); every symbol include/gan_amd.h declares
 SYMBOLS = {
     "gan_conv2d_fwd": (C.c_int, [C.POINTER(GanConvDesc), C.c_void_p]),
@@ -182,6 +187,8 @@ SYMBOLS = {
     "gan_l1": (C.c_int, [C.c_int32, C.POINTER(GanTensor), C.POINTER(GanTensor), C.c_float, C.c_int32, C.c_void_p,
                          C.c_float, C.POINTER(GanTensor), C.c_void_p, C.c_void_p, C.c_void_p]),
     "gan_adam_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "gan_adam_begin_sched": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(GanLrSchedule), C.c_float, C.c_float, C.c_void_p,
+                                       C.c_void_p]),
     "gan_adam_tf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
                               C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
     "gan_sum3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

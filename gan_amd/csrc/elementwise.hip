@@ -2,6 +2,7 @@
 // with fused gradients, TF-form Adam, weight layout preparation, BatchNorm folding for inference mode, dropout-mask
 // generation and fp32<->typed packing.  Reductions are two-stage and deterministic, never atomics.
 #include "common.h"
+#include <cfloat>
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
@@ -141,6 +142,21 @@ __global__ void adam_begin_kernel(int32_t* step, float* lr_t, float lr, float b1
   *step = t;
   double v = (double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t));
   *lr_t = (float)v;
+}
+// the same with the rate of update i = t - 1 on a linear decay (GanLrSchedule, by value): lr * f(i), f = 1 before d0, ef from d1 on.
+// f == 1.0 leaves the product above as it is (lr * 1.0 is exact), f == 0 gives +0 for both outputs (lr > 0, ef never -0: host).
+__global__ void adam_begin_sched_kernel(int32_t* step, float* lr_t, float* lr_now, float lr, float ef, int32_t d0, int32_t d1,
+                                        float b1, float b2, const float* ls) {
+  if (ls && ls[3] != 0.f) return;        // skipped step: iterations, lr_t and lr_now stay
+  int t = *step + 1;
+  *step = t;
+  const int i = t - 1;
+  double f = 1.0;
+  if (i >= d1) f = (double)ef;
+  else if (i >= d0) f = (double)ef + (1.0 - (double)ef) * (double)(d1 - i) / (double)(d1 - d0);
+  double v = (double)lr * f * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t));
+  *lr_t = (float)v;
+  if (lr_now) *lr_now = (float)((double)lr * f);
 }
 // GW: the gradient is read from the data-parallel wire buffer (bf16, summed over ranks) instead of the fp32 gradient buffer
 __device__ __forceinline__ float4 ld_grad4(const void* g, size_t i4, bool wire) {
@@ -665,6 +681,19 @@ int gan_l1(int32_t dtype, const GanTensor* a, const GanTensor* b, float loss_sca
 int gan_adam_begin(int32_t* step, float* lr_t, float lr, float beta1, float beta2, const float* scale_state, gan_stream_t stream) {
   if (!step || !lr_t) return GAN_E_ARG;
   GAN_LAUNCH(adam_begin_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, lr_t, lr, beta1, beta2, scale_state);
+  GAN_CHECK_LAUNCH();
+  return 0;
+}
+
+int gan_adam_begin_sched(int32_t* step, float* lr_t, float* lr_now, const GanLrSchedule* s, float beta1, float beta2,
+                         const float* scale_state, gan_stream_t stream) {
+  if (!step || !lr_t || !s || s->struct_size != sizeof(GanLrSchedule)) return GAN_E_ARG;
+  if (!(s->lr > 0.f) || s->lr > FLT_MAX) return GAN_E_ARG;                        // (NaN fails the first comparison)
+  if (!(s->end_factor >= 0.f && s->end_factor <= 1.f)) return GAN_E_ARG;
+  if (s->decay_start < 0 || s->decay_end <= s->decay_start) return GAN_E_ARG;
+  const float ef = s->end_factor == 0.f ? 0.f : s->end_factor;                    // (-0 -> +0: the floor's outputs are +0)
+  GAN_LAUNCH(adam_begin_sched_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step, lr_t, lr_now, s->lr, ef, s->decay_start,
+             s->decay_end, beta1, beta2, scale_state);
   GAN_CHECK_LAUNCH();
   return 0;
 }

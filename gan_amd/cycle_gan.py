@@ -17,7 +17,7 @@ from .base_gan import GAN
 from .checkpoint import Checkpoint, CheckpointManager, latest_checkpoint
 from .ema import WeightAverage
 from .steps import CycleGANStep
-from .runner import Run, plot_loss_curves, run_epochs, save_panels
+from .runner import Run, add_lr_decay_flags, check_lr_decay_flags, lr_schedule_for, plot_loss_curves, run_epochs, save_panels
 from .utils import cyclegan_losses
 
 
@@ -39,6 +39,8 @@ class CycleGAN(GAN):
         self.dist = ddp.DistInfo(0, 1, self.config.get('device'))
         self._rng = np.random.default_rng(seed)
         self.sync = None
+        self.lr_schedule = None   # nets.LrSchedule of the training steps: fit() derives it from the config
+        self.learning_rates = []  # ... and notes generator_g's rate at the end of every epoch
         # moving averages of the two generators' weights: every replayed training step moves both
         self.generator_g_ema = self.generator_f_ema = None
         ema_decay = float(self.config.get('ema_decay', 0.0))
@@ -125,7 +127,7 @@ class CycleGAN(GAN):
             st = CycleGANStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
                               lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
                               seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=tuple(m.net for m in self._models()),
-                              gan_loss=self.config.get('gan_loss', 'bce'))
+                              gan_loss=self.config.get('gan_loss', 'bce'), lr_schedule=self.lr_schedule if training else None)
             st.sync = self.sync
             if training and self.generator_g_ema is not None:
                 st.ema = (self.generator_g_ema, self.generator_f_ema)
@@ -177,11 +179,20 @@ class CycleGAN(GAN):
         sample = lambda epoch: self.generate_images(self.generator_g, example[:1], os.path.join(samples, f"epoch_{epoch}.png"))
         if not self.dist.is_main:
             save = sample = (lambda *a: None)
+        # (the zip of the two unpaired sets stops at the shorter one: that many updates per epoch)
+        self.lr_schedule = lr_schedule_for(self.config, min(len(train_X), len(train_Y)))      # before the first training step is built
+        self.learning_rates = []
+        after_epoch = None
+        if self.lr_schedule is not None:
+            def after_epoch(epoch):         # generator_g's rate at the epoch's last update, read back from the device: one 4-byte copy
+                lr = next(st for (_, tr), (st, _) in self._steps.items() if tr).current_lr()
+                self.learning_rates.append(lr)
+                return f"learning rate: {lr:.3e}"
         return run_epochs(self.config['epochs'], list(cyclegan_losses()), lambda: self._zipped(train_X, train_Y),
                           lambda: self._zipped(val_X, val_Y), self.train_step, save, sample,
                           ('Total X->Y Generator Loss', 'Discriminator Y Loss'),
                           epoch_mean=lambda acc, n: ddp.mean_over_ranks(acc, n, self.dist),
-                          after_pass=(self.ctx.assert_no_stack_timeout if self.ctx.use_stacks else None))
+                          after_pass=(self.ctx.assert_no_stack_timeout if self.ctx.use_stacks else None), after_epoch=after_epoch)
 
     def predict(self, predict_ds, output_path: str):
         """As Pix2Pix.predict: config['predict_training'] 'false' runs generator_g in inference mode (InstanceNorm has no
@@ -245,6 +256,7 @@ def parse_opt(argv=None):
                         help="--ema-decay: 'true' = decay min(ema-decay, (1 + step) / (10 + step)), so that a young average follows the weights")
     parser.add_argument('--predict-weights', type=str, default='raw', choices=['raw', 'ema'],
                         help="--predict: 'raw' = the checkpoint's generator_g weights; 'ema' = its averaged weights (a run with --ema-decay)")
+    add_lr_decay_flags(parser)
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')
@@ -254,6 +266,7 @@ def parse_opt(argv=None):
     args = parser.parse_args(argv)
     if not 0.0 <= args.ema_decay < 1.0:
         parser.error(f"--ema-decay {args.ema_decay} is outside [0, 1)")
+    check_lr_decay_flags(parser, args)
     assert (args.img_size == 256) or (args.img_size == 512), "img-size currently only supported for 256 x 256 or 512 x 512 pixels!"
     assert (args.validation_size > 0.0 and args.validation_size <= 0.3), "validation size is a proportion and bounded between 0-0.3!"
     assert (args.test_img >= 1), "test-img is an integer and must be >=1!"
@@ -300,6 +313,8 @@ def main(opt):
                     cgan.generate_images(cgan.generator_g, img[None], os.path.join(final, f"img{k}.png"))
                 run.write_json('train_metrics.json', train_metrics)
                 run.write_json('val_metrics.json', val_metrics)
+                if cgan.lr_schedule is not None:
+                    run.write_json('learning_rate.json', cgan.learning_rates)
                 plot_loss_curves(train_metrics, val_metrics, 'CycleGAN', os.path.join(run.root, 'figs'))
                 if info.world > 1:
                     print(f"data-parallel run: {info.world} ranks, replicas in sync.")

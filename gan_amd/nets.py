@@ -55,6 +55,49 @@ class ConvPlan(NamedTuple):
     partial_ptr: int      # where the partials live: behind the launch's own scratch (split-K slabs) in the lane workspace
 
 
+class LrSchedule(NamedTuple):
+    """Linear learning-rate decay over the 0-based update index i (include/gan_amd.h, GanLrSchedule): lr up to
+    decay_start, then a straight line that reaches lr * end_factor at decay_end and stays there.  The device evaluates it from its own
+    step counter (gan_adam_begin_sched); factor() restates it on the host."""
+    lr: float
+    end_factor: float
+    decay_start: int
+    decay_end: int
+
+    def validate(self):
+        """Raises ValueError for what gan_adam_begin_sched refuses; returns self."""
+        with np.errstate(over='ignore'):              # (a rate beyond fp32 becomes inf and is refused below)
+            lr, ef = float(np.float32(self.lr)), float(np.float32(self.end_factor))
+        if not (np.isfinite(lr) and lr > 0.0):
+            raise ValueError(f"LrSchedule: lr {self.lr!r} must be finite and > 0")
+        if not 0.0 <= ef <= 1.0:
+            raise ValueError(f"LrSchedule: end_factor {self.end_factor!r} must lie in [0, 1]")
+        for v in (self.decay_start, self.decay_end):
+            if int(v) != v or not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError(f"LrSchedule: update index {v!r} is not a 32-bit integer")
+        if self.decay_start < 0:
+            raise ValueError(f"LrSchedule: decay_start {self.decay_start} must be >= 0")
+        if self.decay_end <= self.decay_start:
+            raise ValueError(f"LrSchedule: decay_end {self.decay_end} must be > decay_start {self.decay_start}")
+        return self
+
+    def factor(self, i):
+        """f(i): the share of lr that update i runs at (double arithmetic from the fp32-rounded end_factor, as the kernel's)."""
+        ef = float(np.float32(self.end_factor))
+        if i < self.decay_start:
+            return 1.0
+        if i >= self.decay_end:
+            return ef
+        return ef + (1.0 - ef) * float(self.decay_end - i) / float(self.decay_end - self.decay_start)
+
+    def lr_at(self, i):
+        """The rate of update i as the device reports it (lr_now): one rounding to fp32."""
+        return float(np.float32(float(np.float32(self.lr)) * self.factor(i)))
+
+    def desc(self):
+        return L.GanLrSchedule(float(self.lr), float(self.end_factor), int(self.decay_start), int(self.decay_end))
+
+
 class BwdKey(NamedTuple):
     """The arguments of one backward build (GenCall._build_bwd): the key of its plan."""
     use_dgen2: bool = False
@@ -342,7 +385,24 @@ class ParamSet:
             cache[cut_names] = [self._kernel_table(names[a:b]) for a, b in zip(ks[:-1], ks[1:])]
         self._segments = cache[cut_names]
 
+    lr_schedule = None           # LrSchedule: the step counter's launch evaluates it (gan_adam_begin_sched); None: the constant rate
+    lr_now = None                # device scalar: the rate of the last update that ran, written by that launch
+
+    def set_lr_schedule(self, schedule):
+        """Linear decay of this network's Adam rate (LrSchedule), or None for the constant rate of the caller's `lr`.  Op lists
+        built from now on carry it - set it before a step is captured; a captured graph keeps the schedule it was captured with."""
+        if schedule is None:
+            self.lr_schedule = self._lr_desc = None
+            return
+        self.lr_schedule = LrSchedule(*schedule).validate()
+        self._lr_desc = self.lr_schedule.desc()       # (read at every enqueue: lives as long as the op lists that point at it)
+        if self.lr_now is None:                       # (holds the base rate until the first update has run)
+            self.lr_now = torch.full((1,), float(self.lr_schedule.lr), dtype=torch.float32, device=self.ctx.device)
+
     def adam_begin_ops(self, lr, b1, b2):
+        if self.lr_schedule is not None:              # (the schedule holds the base rate: `lr` is the constant-rate argument)
+            return [Op(self.ctx.lib.gan_adam_begin_sched, (self.step.data_ptr(), self.lr_t.data_ptr(), self.lr_now.data_ptr(),
+                                                           C.byref(self._lr_desc), b1, b2, self.ctx.ls_ptr), "adam_begin_sched")]
         return [Op(self.ctx.lib.gan_adam_begin, (self.step.data_ptr(), self.lr_t.data_ptr(), lr, b1, b2, self.ctx.ls_ptr), "adam_begin")]
 
     def adam_segment_ops(self, seg, b1, b2, eps=1e-7, grad_scale=1.0, vectors=False, kernels=True, wire_ptr=None):
@@ -428,7 +488,7 @@ class ParamSet:
         table_ptr, n_ents, tiles, dt = self._prep_args
         gw = 1 if wire_ptr else 0
         ptrs = (self.master.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), wire_ptr or self.grad.data_ptr())
-        ops = [Op(lib.gan_adam_begin, (self.step.data_ptr(), self.lr_t.data_ptr(), lr, b1, b2, self.ctx.ls_ptr), "adam_begin"),
+        ops = self.adam_begin_ops(lr, b1, b2) + [
                Op(lib.gan_adam_prepare_multi, (table_ptr, n_ents, tiles, dt) + ptrs + (self.lr_t.data_ptr(), b1, b2, eps, grad_scale, self.ctx.ls_ptr, gw),
                 "adam_prepare_multi")]
         nvec = self.total - self.vec_start

@@ -18,7 +18,7 @@ from .checkpoint import Checkpoint, CheckpointManager, latest_checkpoint
 from .ema import WeightAverage
 from .quality import QualityMeter, image_quality, summary
 from .steps import Pix2PixStep
-from .runner import Run, plot_loss_curves, run_epochs, save_panels
+from .runner import Run, add_lr_decay_flags, check_lr_decay_flags, lr_schedule_for, plot_loss_curves, run_epochs, save_panels
 from .utils import pix2pix_losses
 
 
@@ -26,6 +26,7 @@ def _step_state(ctx, st):
     """Device state a warm-up pass of capture() advances besides weights and Adam moments: the fp16 loss-scale state and the
     per-call dropout draw counters (every new batch size captures a new step: without this each capture would move them)."""
     ts = [ctx.ls] if ctx.ls is not None else []
+    ts += [net.params.lr_now for net in st.nets() if net.params.lr_now is not None]       # (the rate a scheduled update reports)
     for call in vars(st).values():
         md = getattr(call, 'mask_draws', None)
         if isinstance(md, torch.Tensor):
@@ -69,6 +70,8 @@ class Pix2Pix(GAN):
         self.dist = ddp.DistInfo(0, 1, self.config.get('device'))      # main() replaces it in a data-parallel run
         self._rng = np.random.default_rng(seed)
         self.sync = None          # gan_amd.ddp.GradSync for data-parallel training
+        self.lr_schedule = None   # nets.LrSchedule of the training steps: fit() derives it from the config
+        self.learning_rates = []  # ... and notes the generator's rate at the end of every epoch
         # moving average of the generator weights: every replayed training step moves it
         self.generator_ema = None
         ema_decay = float(self.config.get('ema_decay', 0.0))
@@ -143,7 +146,8 @@ class Pix2Pix(GAN):
             st = Pix2PixStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
                              lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
                              seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net),
-                             generator_loss=self.config.get('generator_loss', 'l1'), gan_loss=self.config.get('gan_loss', 'bce'))
+                             generator_loss=self.config.get('generator_loss', 'l1'), gan_loss=self.config.get('gan_loss', 'bce'),
+                             lr_schedule=self.lr_schedule if training else None)
             st.sync = self.sync
             if training and self.generator_ema is not None:
                 st.ema = (self.generator_ema,)
@@ -226,6 +230,8 @@ class Pix2Pix(GAN):
             save = sample = (lambda *a: None)
         self.val_quality = {'SSIM': [], 'PSNR': [], 'MAE': []}
         self.val_quality_ema = {'SSIM': [], 'PSNR': [], 'MAE': []}
+        self.lr_schedule = lr_schedule_for(self.config, len(train_ds))      # (before the first training step is built and captured)
+        self.learning_rates = []
         after_epoch = None
         if str(self.config.get('quality_metrics', 'false')) == 'true':
             def val_pass(into):         # validation set in inference mode; epoch means over all ranks' images, as the losses
@@ -243,6 +249,14 @@ class Pix2Pix(GAN):
                     with self.generator_ema.averaged():
                         line += " | averaged weights: " + val_pass(self.val_quality_ema)
                 return line
+        if self.lr_schedule is not None:
+            quality_lines = after_epoch
+
+            def after_epoch(epoch):         # the rate of the epoch's last update, read back from the device: one 4-byte copy
+                lr = next(st for (_, tr), (st, _) in self._steps.items() if tr).current_lr()
+                self.learning_rates.append(lr)
+                line = quality_lines(epoch) if quality_lines is not None else None
+                return f"learning rate: {lr:.3e}" + (f"\n{line}" if line else "")
         return run_epochs(self.config['epochs'], list(pix2pix_losses()), lambda: train_ds, lambda: val_ds, self.train_step,
                           save, sample, ('Generator Total Loss', 'Discriminator Loss'),
                           epoch_mean=lambda acc, n: ddp.mean_over_ranks(acc, n, self.dist),
@@ -363,6 +377,7 @@ def parse_opt(argv=None):
                         help="--ema-decay: 'true' = decay min(ema-decay, (1 + step) / (10 + step)), so that a young average follows the weights")
     parser.add_argument('--predict-weights', type=str, default='raw', choices=['raw', 'ema'],
                         help="--predict: 'raw' = the checkpoint's generator weights; 'ema' = its averaged weights (a run with --ema-decay)")
+    add_lr_decay_flags(parser)
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')
@@ -379,6 +394,7 @@ def parse_opt(argv=None):
                      "for 1 - SSIM(generated, target)")
     if not 0.0 <= args.ema_decay < 1.0:
         parser.error(f"--ema-decay {args.ema_decay} is outside [0, 1)")
+    check_lr_decay_flags(parser, args)
     assert (args.img_size == 256) or (args.img_size == 512), "img-size currently only supported for 256 x 256 or 512 x 512 pixels!"
     if args.tile_overlap is None:
         args.tile_overlap = args.img_size // 4
@@ -443,6 +459,8 @@ def main(opt):
                     p2p.generate_images(p2p.generator, inp[None], tar[None], os.path.join(final, f"img{k}.png"))
                 run.write_json('train_metrics.json', train_metrics)
                 run.write_json('val_metrics.json', val_metrics)
+                if p2p.lr_schedule is not None:
+                    run.write_json('learning_rate.json', p2p.learning_rates)
                 plot_loss_curves(train_metrics, val_metrics, 'Pix2Pix', os.path.join(run.root, 'figs'))
                 if info.world > 1:
                     print(f"data-parallel run: {info.world} ranks, replicas in sync.")

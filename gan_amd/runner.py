@@ -58,6 +58,49 @@ class Run:
             self._saved = None
 
 
+def add_lr_decay_flags(parser) -> None:
+    """--lr-decay-epochs / --lr-end-factor of both drivers.  Their defaults are None so that
+    check_lr_decay_flags can tell a given flag from an absent one; it fills in 0 and 0.0."""
+    parser.add_argument('--lr-decay-epochs', type=int, default=None,
+                        help='--train: decay the Adam learning rate linearly over the last N epochs, evaluated on the GPU per step '
+                             '(default 0 = constant rate, the reference)')
+    parser.add_argument('--lr-end-factor', type=float, default=None,
+                        help='--lr-decay-epochs: share of --learning-rate that is left at the end of the run, 0 ..= 1 (default 0.0)')
+
+
+def check_lr_decay_flags(parser, args) -> None:
+    given = [f for f, v in (('--lr-decay-epochs', args.lr_decay_epochs), ('--lr-end-factor', args.lr_end_factor)) if v is not None]
+    if given and args.predict:
+        parser.error(f"{' / '.join(given)}: the learning-rate schedule belongs to --train, not to --predict")
+    if args.lr_decay_epochs is None:
+        args.lr_decay_epochs = 0
+    if args.lr_end_factor is None:
+        args.lr_end_factor = 0.0
+    if args.lr_decay_epochs < 0:
+        parser.error(f"--lr-decay-epochs {args.lr_decay_epochs} is negative")
+    if args.train and args.lr_decay_epochs > args.epochs:
+        parser.error(f"--lr-decay-epochs {args.lr_decay_epochs} is more than --epochs {args.epochs}")
+    if not 0.0 <= args.lr_end_factor <= 1.0:
+        parser.error(f"--lr-end-factor {args.lr_end_factor} is outside [0, 1]")
+
+
+def lr_schedule_for(config, steps_per_epoch: int):
+    """The LrSchedule of a run's config, or None (--lr-decay-epochs 0: the constant rate, nothing is built): the rate is held for
+    the first epochs - N epochs and decays over the updates of the last N.  steps_per_epoch: training batches per epoch of this
+    replica (data parallel: the same on every rank, ddp.shard_files)."""
+    from .nets import LrSchedule
+    n = int(config.get('lr_decay_epochs') or 0)
+    if n == 0:
+        return None
+    epochs = int(config['epochs'])
+    if not 0 < n <= epochs:
+        raise ValueError(f"lr_decay_epochs {n} is outside [0, epochs = {epochs}]")
+    if steps_per_epoch <= 0:
+        raise ValueError("the learning-rate schedule needs at least one training batch per epoch")
+    return LrSchedule(float(config['learning_rate']), float(config.get('lr_end_factor') or 0.0), (epochs - n) * steps_per_epoch,
+                      epochs * steps_per_epoch).validate()
+
+
 def save_panels(path: str, panels, gray: bool) -> None:
     """Side-by-side image panels [(title, HWC array in [-1, 1])] -> one PNG at dpi 200."""
     import matplotlib

@@ -17,7 +17,7 @@ from typing import NamedTuple
 import torch
 
 from . import _lib as L
-from .nets import Ctx, DiscriminatorNet, GeneratorNet
+from .nets import Ctx, DiscriminatorNet, GeneratorNet, LrSchedule
 
 
 # Other threads of the process may call into the runtime while a step is being captured (the RCCL watchdog of
@@ -77,6 +77,28 @@ class _StepBase:
         self.sync = None             # GradSync for data-parallel runs
         self.ema = ()                # WeightAverage objects (gan_amd/ema.py) a replayed training step moves, DESIGN.md section 15
         self._in_step = _InStepAdam()
+
+    def _set_lr_schedule(self, schedule):
+        """A linear decay of the Adam rate (nets.LrSchedule) for every network of the step: the launch that
+        advances a network's step counter then evaluates it on the device, in the same place of every schedule of this file.  None
+        leaves the networks as they are: objects shared with another step (nets=...) keep what that step gave them."""
+        self.lr_schedule = None
+        if schedule is None:
+            return
+        schedule = LrSchedule(*schedule).validate()
+        if float(schedule.lr) != float(self.lr):
+            raise ValueError(f"lr_schedule.lr {schedule.lr!r} differs from the step's lr {self.lr!r}")
+        self.lr_schedule = schedule
+        for net in self.nets():
+            net.params.set_lr_schedule(schedule)
+
+    def current_lr(self, net=0):
+        """The rate of the last update network `net` (index into nets()) ran, read back from the device: a 4-byte copy that waits
+        for the stream - once per epoch, not per step.  Without a schedule, or before the first update: the base rate."""
+        P = self.nets()[net].params
+        if P.lr_schedule is None:
+            return float(self.lr)
+        return float(P.lr_now.item())
 
     def _example_inputs(self):
         sh = (self.B, self.S, self.S, self.C)
@@ -286,7 +308,7 @@ class Pix2PixStep(_StepBase):
     ddp_wire_direct = True       # bf16 all-reduce exchange: wgrad launches write their gradients straight into the wire buffer
 
     def __init__(self, ctx: Ctx, batch, size, channels=1, lam=100.0, lr=2e-4, beta_1=0.5, beta_2=0.999,
-                 seed=123, dropout=True, nets=None, mask_stream=0, generator_loss='l1', gan_loss='bce'):
+                 seed=123, dropout=True, nets=None, mask_stream=0, generator_loss='l1', gan_loss='bce', lr_schedule=None):
         if generator_loss not in ('l1', 'dssim'):
             raise ValueError(f"generator_loss {generator_loss!r}: 'l1' or 'dssim'")
         super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=8, gan_loss=gan_loss)
@@ -304,6 +326,7 @@ class Pix2PixStep(_StepBase):
         self.g = self.G.new_call(batch, size, dropout=dropout, seed=seed, stream_id=mask_stream,   # mask_stream: train / val steps draw different masks
                                  wgrads_on_side_lane=ctx.lanes)
         self.d = self.D.new_call(batch, size, calls=2)
+        self._set_lr_schedule(lr_schedule)
 
     def nets(self):
         return (self.G, self.D)
@@ -590,7 +613,7 @@ class CycleGANStep(_StepBase):
     wide_wgrads = True           # ... one wgrad GEMM per layer over a generator's three invocations (host + guest call)
 
     def __init__(self, ctx: Ctx, batch, size, channels=1, lam=10.0, lr=2e-4, beta_1=0.5, beta_2=0.999,
-                 seed=123, dropout=True, nets=None, mask_stream=0, merged=True, gan_loss='bce'):
+                 seed=123, dropout=True, nets=None, mask_stream=0, merged=True, gan_loss='bce', lr_schedule=None):
         super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=12, gan_loss=gan_loss)     # [0..8] as below; [9] cycle term of chain B; [10] stays 0
         n = 'instancenorm'                                                    # cycle_gan.py:30-33
         if nets is not None:
@@ -637,6 +660,7 @@ class CycleGANStep(_StepBase):
             self.dy = self.Dy.new_call(batch, size, calls=2)
         self.l1_ws_b = torch.zeros(4096, dtype=torch.float32, device=ctx.device)   # chain B's loss kernels run beside chain A's
         self.bce_ws_b = torch.zeros(1024, dtype=torch.float32, device=ctx.device)
+        self._set_lr_schedule(lr_schedule)
 
     def nets(self):
         return (self.Gg, self.Gf, self.Dx, self.Dy)

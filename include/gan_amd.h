@@ -393,8 +393,30 @@ int gan_sum3(const float* a, const float* b, const float* c, float* out, int32_t
 /* ---- optimiser ------------------------------------------------------------------------------ */
 /* tf.keras.optimizers.Adam (base_gan.py:247-252), TF form: lr_t = lr*sqrt(1-b2^t)/(1-b1^t);
  * m += (g-m)(1-b1); v += (g*g-v)(1-b2); p -= lr_t*m/(sqrt(v)+eps).  `step` is a device counter:
- * gan_adam_begin increments it and writes lr_t, so a captured graph advances correctly on replay. */
+ * gan_adam_begin increments it and writes lr_t, so a captured graph advances correctly on replay.  `lr` is a by-value
+ * argument: a captured graph holds it for good.  A rate that changes during the run: gan_adam_begin_sched below. */
 int gan_adam_begin(int32_t* step, float* lr_t, float lr, float beta1, float beta2, const float* scale_state, gan_stream_t stream);
+/* Linear learning-rate decay as a function of the device step counter (no counterpart in the reference, whose rate is constant; the
+ * Pix2Pix / CycleGAN papers' schedule): update index i = t - 1 (0-based) runs at lr * f(i),
+ *   f(i) = 1                                                                       i <  decay_start
+ *        = end_factor + (1 - end_factor) * (decay_end - i) / (decay_end - decay_start)   decay_start <= i < decay_end
+ *        = end_factor                                                              i >= decay_end
+ * so f(decay_start) = 1 (no jump) and the last decayed update, decay_end - 1, is still above the floor. */
+typedef struct GanLrSchedule {
+  uint32_t struct_size;
+  float    lr;           /* base learning rate */
+  float    end_factor;   /* share of lr that is left from decay_end on, 0 ..= 1 */
+  int32_t  decay_start;  /* first 0-based update index that is decayed */
+  int32_t  decay_end;    /* from this update index on: lr * end_factor */
+} GanLrSchedule;
+/* gan_adam_begin with the rate of the schedule: t = *step + 1 is stored, lr_now (device, one float, may be NULL) receives
+ * (float)(lr * f(t - 1)) and lr_t (float)(lr * f(t - 1) * sqrt(1-b2^t)/(1-b1^t)), double arithmetic from the fp32 arguments, one
+ * rounding each; where f = 1 lr_t has the bits gan_adam_begin writes, where f = 0 both are +0.  A skipped step (scale_state[3] != 0)
+ * leaves step, lr_t and lr_now alone.  The schedule is read at enqueue (a captured graph holds it by value) and advances with the
+ * counter on replay.  GAN_E_ARG and no launch: NULL step / lr_t / s, a struct_size this library was not built with, lr not finite
+ * or <= 0, end_factor outside [0, 1], decay_start < 0, decay_end <= decay_start. */
+int gan_adam_begin_sched(int32_t* step, float* lr_t, float* lr_now, const GanLrSchedule* s, float beta1, float beta2,
+                         const float* scale_state, gan_stream_t stream);
 /* grad: fp32 [count], or with grad_bf16 != 0 the bfloat16 wire buffer of the data-parallel exchange (gan_grad_pack, summed
  * over ranks): Adam then reads the exchanged gradient where it landed, grad_scale = 1/world (8-byte aligned). */
 int gan_adam_tf(float* param, float* m, float* v, const void* grad, int64_t count, const float* lr_t,
