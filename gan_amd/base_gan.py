@@ -12,6 +12,7 @@ state: for CycleGAN only the dropout differs."""
 from __future__ import annotations
 
 import ctypes as C
+import os
 from abc import ABC, abstractmethod
 
 import numpy as np
@@ -19,9 +20,12 @@ import torch
 
 from . import _lib as L
 from . import data as D
+from . import ddp
 from . import tiling
 from .checkpoint import DISC_LAYERS, GEN_LAYERS, tf_variable_key
+from .ema import WeightAverage
 from .nets import Ctx, DiscriminatorNet, GeneratorNet, workspace_mb_for
+from .runner import lr_schedule_for, run_epochs
 
 
 def _to_dev(x, ctx):
@@ -174,6 +178,23 @@ class AdamConfig:
                     ps.tensor(name, slot).copy_(torch.from_numpy(sd[k].astype(np.float32)).view(ps.entries[name][1]))
 
 
+def _step_state(ctx, st):
+    """Device state a warm-up pass of capture() advances besides weights and Adam moments: the fp16 loss-scale state and the
+    per-call dropout draw counters (every new batch size captures a new step: without this each capture would move them)."""
+    ts = [ctx.ls] if ctx.ls is not None else []
+    ts += [net.params.lr_now for net in st.nets() if net.params.lr_now is not None]       # (the rate a scheduled update reports)
+    for call in vars(st).values():
+        md = getattr(call, 'mask_draws', None)
+        if isinstance(md, torch.Tensor):
+            ts.append(md)
+    return [(t, t.clone()) for t in ts]
+
+
+def _restore_step_state(saved):
+    for t, v in saved:
+        t.copy_(v)
+
+
 class GAN(ABC):
     def __init__(self, config):
         self.config = config
@@ -230,6 +251,101 @@ class GAN(ABC):
 
     def optimizer(self, learning_rate: float = 2e-4, beta_1: float = 0.5, beta_2: float = 0.999):
         return AdamConfig(learning_rate, beta_1, beta_2)
+
+    # ---- trainer core: what Pix2Pix and CycleGAN share around their captured steps (no counterpart in the reference) ----------
+    def _init_trainer(self, averaged):
+        """Called by a model's __init__ once its networks exist.  averaged: the generators whose weights get a moving average
+        (the first one is the generator that predicts) -> one WeightAverage per generator, or None each
+        without --ema-decay / --predict-weights ema."""
+        self._steps = {}          # (batch, training) -> (step object, graph replay)
+        self.dist = ddp.DistInfo(0, 1, self.config.get('device'))      # enable_data_parallel() replaces it in a data-parallel run
+        self._rng = np.random.default_rng(int(self.config.get('seed', 123)))
+        self.sync = None          # gan_amd.ddp.GradSync for data-parallel training
+        self.lr_schedule = None   # nets.LrSchedule of the training steps (DESIGN.md section 17): fit() derives it from the config
+        self.learning_rates = []  # ... and notes the rate of networks()[0] at the end of every epoch
+        self.averages = ()        # every replayed training step moves them
+        ema_decay = float(self.config.get('ema_decay', 0.0))
+        if ema_decay > 0 or str(self.config.get('predict_weights', 'raw')) == 'ema':
+            warmup = str(self.config.get('ema_warmup', 'true')) == 'true'
+            self.averages = tuple(WeightAverage(g, ema_decay, warmup) for g in averaged)
+        return self.averages or (None,) * len(averaged)
+
+    def _ema_active(self):
+        return bool(self.averages) and self.averages[0].decay > 0
+
+    def enable_data_parallel(self, info, wire='bf16', exchange='allreduce'):
+        """One process per GPU (torchrun): gradients are averaged over the ranks with RCCL all-reduces overlapped with the
+        backward pass (gan_amd/steps.py); normalisation statistics stay per replica; the augmentation stream and the dropout
+        masks differ per rank.  The reference is single-device (base_gan.py:18-19 only prints the GPU count)."""
+        self.dist = info
+        if info.world > 1:
+            self._rng = np.random.default_rng(int(self.config.get('seed', 123)) + 7919 * info.rank)
+            self.sync = ddp.GradSync([m.net.params.grad for m in self.networks()], compress_bf16=(wire == 'bf16'), lib=self.ctx.lib,
+                                     exchange=exchange)
+
+    def _step_for(self, batch, training):
+        key = (batch, bool(training))
+        if key not in self._steps:
+            st = self._build_step(batch, training)
+            st.sync = self.sync
+            if training:
+                st.ema = self.averages
+            saved = self._snapshot()       # capture() runs warm-up passes (they also move BatchNorm's moving statistics): undo them
+            extra = _step_state(self.ctx, st)
+            replay = st.capture(training=training)
+            self._restore(saved)
+            _restore_step_state(extra)
+            self._steps[key] = (st, replay)
+        return self._steps[key]
+
+    def _snapshot(self):
+        return [(ps, ps.master.clone(), ps.m.clone(), ps.v.clone(), ps.step.clone(), {k: v.clone() for k, v in ps.state.items()})
+                for ps in (m.net.params for m in self.networks())]
+
+    def _restore(self, saved):
+        for ps, w, m, v, step, state in saved:
+            ps.master.copy_(w); ps.m.copy_(m); ps.v.copy_(v); ps.step.copy_(step)
+            for k, t in state.items():
+                ps.state[k].copy_(t)
+            ps.prepare()
+
+    def _with_lr_line(self, after_epoch=None):
+        """after_epoch of run_epochs with the learning-rate line in front (a run with a schedule only)."""
+        if self.lr_schedule is None:
+            return after_epoch
+
+        def lr_line(epoch):         # the rate of networks()[0] at the epoch's last update, read back from the device: one 4-byte copy
+            lr = next(st for (_, tr), (st, _) in self._steps.items() if tr).current_lr()
+            self.learning_rates.append(lr)
+            line = after_epoch(epoch) if after_epoch is not None else None
+            return f"learning rate: {lr:.3e}" + (f"\n{line}" if line else "")
+        return lr_line
+
+    def _fit(self, output_path, checkpoint_manager, keys, train_batches, val_batches, steps_per_epoch, headline, sampler, after_epoch=None):
+        """The tail of fit(): train_batches() / val_batches() yield the arguments of train_step, steps_per_epoch updates per epoch;
+        sampler(path) draws the sample image of an epoch.  Rank 0 alone writes checkpoints and sample images."""
+        samples = os.path.join(output_path, 'test_images')
+        if self.dist.is_main:
+            os.makedirs(samples, exist_ok=True)
+        save = checkpoint_manager.save if checkpoint_manager is not None else (lambda: None)
+        sample = lambda epoch: sampler(os.path.join(samples, f"epoch_{epoch}.png"))
+        if not self.dist.is_main:
+            save = sample = (lambda *a: None)
+        self.lr_schedule = lr_schedule_for(self.config, steps_per_epoch)      # (before the first training step is built and captured)
+        self.learning_rates = []
+        return run_epochs(self.config['epochs'], list(keys), train_batches, val_batches, self.train_step, save, sample, headline,
+                          epoch_mean=lambda acc, n: ddp.mean_over_ranks(acc, n, self.dist),
+                          after_pass=(self.ctx.assert_no_stack_timeout if self.ctx.use_stacks else None),
+                          after_epoch=self._with_lr_line(after_epoch))
+
+    @abstractmethod
+    def networks(self):
+        """The model objects, generators first, in the order their step object takes them: every loop over the ParamSets goes
+        through it."""
+
+    @abstractmethod
+    def _build_step(self, batch, training):
+        """-> the model's step object (gan_amd/steps.py) of this batch size on the model's networks, not yet captured."""
 
     # ---- abstract surface, as in the reference (base_gan.py:254-292) ----------------------------
     @abstractmethod

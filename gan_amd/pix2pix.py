@@ -14,29 +14,10 @@ from . import data as D
 from . import ddp
 from . import tiling
 from .base_gan import GAN
-from .checkpoint import Checkpoint, CheckpointManager, latest_checkpoint
-from .ema import WeightAverage
 from .quality import QualityMeter, image_quality, summary
 from .steps import Pix2PixStep
-from .runner import Run, add_lr_decay_flags, check_lr_decay_flags, lr_schedule_for, plot_loss_curves, run_epochs, save_panels
+from .runner import add_common_flags, check_common_flags, drive, save_panels
 from .utils import pix2pix_losses
-
-
-def _step_state(ctx, st):
-    """Device state a warm-up pass of capture() advances besides weights and Adam moments: the fp16 loss-scale state and the
-    per-call dropout draw counters (every new batch size captures a new step: without this each capture would move them)."""
-    ts = [ctx.ls] if ctx.ls is not None else []
-    ts += [net.params.lr_now for net in st.nets() if net.params.lr_now is not None]       # (the rate a scheduled update reports)
-    for call in vars(st).values():
-        md = getattr(call, 'mask_draws', None)
-        if isinstance(md, torch.Tensor):
-            ts.append(md)
-    return [(t, t.clone()) for t in ts]
-
-
-def _restore_step_state(saved):
-    for t, v in saved:
-        t.copy_(v)
 
 
 def _dssim_eager(a, b):
@@ -66,27 +47,10 @@ class Pix2Pix(GAN):
                                                    beta_2=self.config['beta_2'])
         self.generator_optimizer = mk().bind(self.generator.net.params)
         self.discriminator_optimizer = mk().bind(self.discriminator.net.params)
-        self._steps = {}          # (batch, training) -> (Pix2PixStep, graph replay)
-        self.dist = ddp.DistInfo(0, 1, self.config.get('device'))      # main() replaces it in a data-parallel run
-        self._rng = np.random.default_rng(seed)
-        self.sync = None          # gan_amd.ddp.GradSync for data-parallel training
-        self.lr_schedule = None   # nets.LrSchedule of the training steps: fit() derives it from the config
-        self.learning_rates = []  # ... and notes the generator's rate at the end of every epoch
-        # moving average of the generator weights: every replayed training step moves it
-        self.generator_ema = None
-        ema_decay = float(self.config.get('ema_decay', 0.0))
-        if ema_decay > 0 or str(self.config.get('predict_weights', 'raw')) == 'ema':
-            self.generator_ema = WeightAverage(self.generator, ema_decay, str(self.config.get('ema_warmup', 'true')) == 'true')
+        (self.generator_ema,) = self._init_trainer(averaged=(self.generator,))
 
-    def enable_data_parallel(self, info, wire='bf16', exchange='allreduce'):
-        """One process per GPU (torchrun): gradients are averaged over the ranks with RCCL all-reduces overlapped with the
-        backward pass (gan_amd/steps.py bucketed schedule); BatchNorm statistics stay per replica; the augmentation stream and
-        the dropout masks differ per rank.  The reference is single-device (base_gan.py:18-19 only prints the GPU count)."""
-        self.dist = info
-        if info.world > 1:
-            self._rng = np.random.default_rng(int(self.config.get('seed', 123)) + 7919 * info.rank)
-            self.sync = ddp.GradSync([self.generator.net.params.grad, self.discriminator.net.params.grad],
-                                     compress_bf16=(wire == 'bf16'), lib=self.ctx.lib, exchange=exchange)
+    def networks(self):
+        return (self.generator, self.discriminator)
 
     # ---- input pipeline (pix2pix.py:34-165) ------------------------------------------------------
     def split_img(self, image_file: str):
@@ -140,38 +104,12 @@ class Pix2Pix(GAN):
         gan_loss2 = _dssim_eager(gen_output, target) if kind == 'dssim' else (target - gen_output).abs().mean()
         return gan_loss + (self.config['lambda'] * gan_loss2), gan_loss, gan_loss2
 
-    def _step_for(self, batch, training):
-        key = (batch, bool(training))
-        if key not in self._steps:
-            st = Pix2PixStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
-                             lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
-                             seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net),
-                             generator_loss=self.config.get('generator_loss', 'l1'), gan_loss=self.config.get('gan_loss', 'bce'),
-                             lr_schedule=self.lr_schedule if training else None)
-            st.sync = self.sync
-            if training and self.generator_ema is not None:
-                st.ema = (self.generator_ema,)
-            saved = self._snapshot()       # capture() runs warm-up passes (they also move BatchNorm's moving statistics): undo them
-            extra = _step_state(self.ctx, st)
-            replay = st.capture(training=training)
-            self._restore(saved)
-            _restore_step_state(extra)
-            self._steps[key] = (st, replay)
-        return self._steps[key]
-
-    def _ema_active(self):
-        return self.generator_ema is not None and self.generator_ema.decay > 0
-
-    def _snapshot(self):
-        return [(ps, ps.master.clone(), ps.m.clone(), ps.v.clone(), ps.step.clone(), {k: v.clone() for k, v in ps.state.items()})
-                for ps in (self.generator.net.params, self.discriminator.net.params)]
-
-    def _restore(self, saved):
-        for ps, w, m, v, step, state in saved:
-            ps.master.copy_(w); ps.m.copy_(m); ps.v.copy_(v); ps.step.copy_(step)
-            for k, t in state.items():
-                ps.state[k].copy_(t)
-            ps.prepare()
+    def _build_step(self, batch, training):
+        return Pix2PixStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
+                           lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
+                           seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net),
+                           generator_loss=self.config.get('generator_loss', 'l1'), gan_loss=self.config.get('gan_loss', 'bce'),
+                           lr_schedule=self.lr_schedule if training else None)
 
     def train_step(self, input_image, target, training: bool = True):
         """-> (gen_total_loss, gen_gan_loss, gen_gan_loss2, disc_loss) as 0-d device tensors (no host sync)."""
@@ -220,18 +158,8 @@ class Pix2Pix(GAN):
         it = iter(test_ds)
         example_input, example_target = next(it)
         it.close()
-        samples = os.path.join(output_path, 'test_images')
-        if self.dist.is_main:
-            os.makedirs(samples, exist_ok=True)
-        save = checkpoint_manager.save if checkpoint_manager is not None else (lambda: None)
-        sample = lambda epoch: self.generate_images(self.generator, example_input[:1], example_target[:1],
-                                                    os.path.join(samples, f"epoch_{epoch}.png"))
-        if not self.dist.is_main:           # rank 0 alone writes checkpoints and sample images
-            save = sample = (lambda *a: None)
         self.val_quality = {'SSIM': [], 'PSNR': [], 'MAE': []}
         self.val_quality_ema = {'SSIM': [], 'PSNR': [], 'MAE': []}
-        self.lr_schedule = lr_schedule_for(self.config, len(train_ds))      # (before the first training step is built and captured)
-        self.learning_rates = []
         after_epoch = None
         if str(self.config.get('quality_metrics', 'false')) == 'true':
             def val_pass(into):         # validation set in inference mode; epoch means over all ranks' images, as the losses
@@ -249,18 +177,9 @@ class Pix2Pix(GAN):
                     with self.generator_ema.averaged():
                         line += " | averaged weights: " + val_pass(self.val_quality_ema)
                 return line
-        if self.lr_schedule is not None:
-            quality_lines = after_epoch
-
-            def after_epoch(epoch):         # the rate of the epoch's last update, read back from the device: one 4-byte copy
-                lr = next(st for (_, tr), (st, _) in self._steps.items() if tr).current_lr()
-                self.learning_rates.append(lr)
-                line = quality_lines(epoch) if quality_lines is not None else None
-                return f"learning rate: {lr:.3e}" + (f"\n{line}" if line else "")
-        return run_epochs(self.config['epochs'], list(pix2pix_losses()), lambda: train_ds, lambda: val_ds, self.train_step,
-                          save, sample, ('Generator Total Loss', 'Discriminator Loss'),
-                          epoch_mean=lambda acc, n: ddp.mean_over_ranks(acc, n, self.dist),
-                          after_pass=(self.ctx.assert_no_stack_timeout if self.ctx.use_stacks else None), after_epoch=after_epoch)
+        return self._fit(output_path, checkpoint_manager, pix2pix_losses(), lambda: train_ds, lambda: val_ds, len(train_ds),
+                         ('Generator Total Loss', 'Discriminator Loss'),
+                         lambda path: self.generate_images(self.generator, example_input[:1], example_target[:1], path), after_epoch)
 
     def predict(self, predict_ds, output_path: str):
         """config['predict_training'] 'true' (default): the reference's batch-1 `generator(x, training=True)` per image.  'false':
@@ -323,67 +242,25 @@ class Pix2Pix(GAN):
 
 
 def parse_opt(argv=None):
-    """Same flags / defaults / assertions as pix2pix.py:341-377 (+ optional --dtype / --device)."""
+    """Same flags / defaults / assertions as pix2pix.py:341-377 (+ this project's: runner.add_common_flags and the ones below)."""
     argv = sys.argv[1:] if argv is None else argv
     parser = argparse.ArgumentParser()
     parser.add_argument('--data', type=str, help='path to data', required=True)
-    parser.add_argument('--output', type=str, help='path to output results', required=True)
-    parser.add_argument('--img-size', type=int, default=256, help='image size h,w')
-    parser.add_argument('--batch-size', type=int, default=1, help='batch size per replica')
-    parser.add_argument('--buffer-size', type=int, default=99999, help='buffer size')
-    parser.add_argument('--channels', type=str, default='1', choices=['1', '3'], help='number of color channels to read in and output')
-    parser.add_argument('--logging', type=str, default='true', choices=['true', 'false'], help='turn on/off script logging, e.g. for CLI debugging')
+    add_common_flags(parser, argv, generator='the generator', networks='generator and discriminator')
     parser.add_argument('--generator-loss', type=str, default='l1', choices=['l1', 'ssim', 'dssim'],
                         help="secondary generator loss: 'l1' = mean |target - generated|; 'dssim' = 1 - mean SSIM(generated, target), computed "
                              "with its gradient on the GPU; 'ssim' (the reference's input-against-target term) is refused")
-    parser.add_argument('--gan-loss', type=str, default='bce', choices=['bce', 'lsgan'],
-                        help="adversarial loss on the discriminator's logits: 'bce' = sigmoid cross-entropy (the reference); "
-                             "'lsgan' = least squares, mean((logit - target)^2)")
     parser.add_argument('--input-img-orient', type=str, default='left', choices=['left', 'right'], help='whether input image is on left (i.e. target right) or vice-versa')
-    parser.add_argument('--seed', type=int, default=123, help='seed value for random number generator')
-    group = parser.add_mutually_exclusive_group(required=True)
-    group.add_argument('--train', action='store_true', help='train model using data')
-    group.add_argument('--predict', action='store_true', help='use pretrained weights to make predictions on data')
-    parser.add_argument('--save-weights', type=str, default='true', choices=['true', 'false'], help='save model checkpoints and weights')
-    parser.add_argument('--epochs', type=int, default=5, help='number of epochs to train', required='--train' in argv)
     parser.add_argument('--lambda', type=int, default=100, help='lambda value for secondary generator loss (L1 / dSSIM)')
-    parser.add_argument('--validation-size', type=float, default=0.1, help='validation set size as share of number of training images')
-    parser.add_argument('--test-img', type=int, default=5, help='number of test images to sample')
-    parser.add_argument('--learning-rate', type=float, default=2e-4, help='learning rate for Adam optimizer for generator and discriminator')
-    parser.add_argument('--beta-1', type=float, default=0.5, help='exponential decay rate for 1st moment of Adam optimizer for generator and discriminator')
-    parser.add_argument('--beta-2', type=float, default=0.999, help='exponential decay rate for 2st moment of Adam optimizer for generator and discriminator')
-    parser.add_argument('--weights', type=str, help='path to pretrained model weights for prediction', required='--predict' in argv)
-    parser.add_argument('--dtype', type=str, default='bf16', choices=['bf16', 'f16', 'f32'], help='MI355X compute/storage dtype (f32 = exact parity path)')
-    parser.add_argument('--predict-training', type=str, default='true', choices=['true', 'false'],
-                        help="--predict only: 'true' = the reference's generator(x, training=True) at batch 1 (batch statistics, "
-                             "dropout); 'false' = Keras inference mode (moving statistics, no dropout) in batches of --batch-size")
     parser.add_argument('--predict-resolution', type=str, default='resized', choices=['resized', 'native'],
                         help="--predict only: 'resized' = every half resized to --img-size first (the reference); 'native' = predict "
                              "at the source size from overlapping --img-size tiles blended on the GPU (needs --predict-training false)")
     parser.add_argument('--tile-overlap', type=int, default=None,
                         help='--predict-resolution native: pixels neighbouring tiles share, 0 ..= img-size / 2 (default img-size / 4)')
-    parser.add_argument('--data-cache', type=str, default='host', choices=['host', 'device'],
-                        help="--train: 'host' decodes and augments every image on the CPU in every epoch; 'device' decodes each file once, "
-                             "keeps the uint8 images in GPU memory and builds every batch there (identical batches)")
-    parser.add_argument('--data-cache-gb', type=float, default=64, help='--data-cache device: most GiB of decoded images to keep per GPU')
     parser.add_argument('--quality-metrics', type=str, default='false', choices=['true', 'false'],
                         help="image quality of the generator against the ground truth (SSIM as tf.image.ssim, PSNR, MAE), computed on "
                              "the GPU: --train writes logs/val_quality.json (per epoch) and logs/test_quality.json, --predict "
                              "writes logs/prediction_metrics.json")
-    parser.add_argument('--ema-decay', type=float, default=0.0,
-                        help='--train: keep an exponential moving average of the generator weights with this decay, updated on the GPU '
-                             'after every step and saved with the checkpoint (0 = off; e.g. 0.999)')
-    parser.add_argument('--ema-warmup', type=str, default='true', choices=['true', 'false'],
-                        help="--ema-decay: 'true' = decay min(ema-decay, (1 + step) / (10 + step)), so that a young average follows the weights")
-    parser.add_argument('--predict-weights', type=str, default='raw', choices=['raw', 'ema'],
-                        help="--predict: 'raw' = the checkpoint's generator weights; 'ema' = its averaged weights (a run with --ema-decay)")
-    add_lr_decay_flags(parser)
-    parser.add_argument('--device', type=str, default='cuda:0')
-    parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
-                        help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')
-    parser.add_argument('--wire', type=str, default='bf16', choices=['bf16', 'f32'], help='gradient all-reduce wire format')
-    parser.add_argument('--exchange', type=str, default='allreduce', choices=['allreduce', 'rs_ag'],
-                        help='gradient exchange: one all-reduce per bucket, or fp32 reduce-scatter + all-gather in the wire format')
     args = parser.parse_args(argv)
     if args.generator_loss == 'ssim':
         # pix2pix.py:182-184 computes tf.image.ssim(input_image, target): no gradient reaches the generator and the total becomes
@@ -392,10 +269,7 @@ def parse_opt(argv=None):
         parser.error("--generator-loss ssim is not supported by gan_amd (the reference's SSIM term compares input with target and "
                      "carries no gradient, pix2pix.py:182-184); use the default --generator-loss l1, or --generator-loss dssim "
                      "for 1 - SSIM(generated, target)")
-    if not 0.0 <= args.ema_decay < 1.0:
-        parser.error(f"--ema-decay {args.ema_decay} is outside [0, 1)")
-    check_lr_decay_flags(parser, args)
-    assert (args.img_size == 256) or (args.img_size == 512), "img-size currently only supported for 256 x 256 or 512 x 512 pixels!"
+    check_common_flags(parser, args)
     if args.tile_overlap is None:
         args.tile_overlap = args.img_size // 4
     if not 0 <= args.tile_overlap <= args.img_size // 2:
@@ -403,76 +277,27 @@ def parse_opt(argv=None):
     if args.predict_resolution == 'native' and not (args.predict and args.predict_training == 'false'):
         parser.error("--predict-resolution native requires --predict and --predict-training false: tiles are only meaningful in "
                      "inference mode (batch statistics over the tiles of one image are not the reference's semantics)")
-    assert (args.validation_size > 0.0 and args.validation_size <= 0.3), "validation size is a proportion and bounded between 0-0.3!"
-    assert (args.test_img >= 1), "test-img is an integer and must be >=1!"
     return args
+
+
+def _write_quality_logs(p2p, run, test):
+    """--quality-metrics true: the per-epoch validation metrics and those of the test set, also on the averaged weights."""
+    if str(p2p.config.get('quality_metrics', 'false')) != 'true':
+        return
+    finite = lambda per_epoch: {k: [v if np.isfinite(v) else None for v in vs] for k, vs in per_epoch.items()}
+    run.write_json('val_quality.json', finite(p2p.val_quality))
+    run.write_json('test_quality.json', summary(p2p.evaluate(test)))
+    if p2p._ema_active():
+        run.write_json('val_quality_ema.json', finite(p2p.val_quality_ema))
+        with p2p.generator_ema.averaged():
+            run.write_json('test_quality_ema.json', summary(p2p.evaluate(test)))
 
 
 def main(opt):
     """`python pix2pix.py --train ...` on one GPU, or `torchrun --nproc-per-node N pix2pix.py --train ...` for data-parallel
-    training: the process group is joined before the first GPU call, rank r owns cuda:r, the training / validation file lists
-    are sharded by rank after the seeded split, and rank 0 alone owns the run directory (logs, checkpoints, figures)."""
-    info = ddp.init_from_env(opt.device, opt.dist_backend)
-    opt.device = info.device or opt.device
-    run = Run(opt.output, log_to_file=opt.logging == 'true' and info.is_main, strict_logs=True, writer=info.is_main)
-    try:
-        p2p = Pix2Pix(vars(opt))
-        if opt.train:
-            p2p.enable_data_parallel(info, opt.wire, opt.exchange)
-        objects = dict(generator_optimizer=p2p.generator_optimizer, discriminator_optimizer=p2p.discriminator_optimizer,
-                       generator=p2p.generator, discriminator=p2p.discriminator)
-        if p2p.generator_ema is not None:      # after `generator`: restore runs in this order, and an average that finds no
-            objects['generator_ema'] = p2p.generator_ema     # weights of its own starts over from the restored generator
-        checkpoint = Checkpoint(**objects)
-        run.write_json('config.json', p2p.config)
-        if opt.predict:
-            if info.is_main:
-                dataset, _, _ = p2p.image_pipeline(predict=True)
-                checkpoint.restore(latest_checkpoint(opt.weights))
-                if opt.predict_weights == 'ema':
-                    if not p2p.generator_ema.loaded:
-                        raise SystemExit(f"--predict-weights ema: checkpoint holds no averaged weights ({opt.weights}); "
-                                         "train with --ema-decay")
-                    with p2p.generator_ema.averaged():
-                        metrics = p2p.predict(dataset, run.root)
-                else:
-                    metrics = p2p.predict(dataset, run.root)
-                if metrics is not None:
-                    run.write_json('prediction_metrics.json', summary(metrics))
-        else:
-            train, validation, test = p2p.image_pipeline(predict=False)
-            manager = (CheckpointManager(checkpoint, os.path.join(run.root, 'training_checkpoints'), max_to_keep=1)
-                       if opt.save_weights == 'true' and info.is_main else None)
-            train_metrics, val_metrics = p2p.fit(train, validation, test, run.root, checkpoint_manager=manager)
-            ddp.assert_replicas_in_sync([p2p.generator.net.params, p2p.discriminator.net.params], info)
-            if info.is_main:
-                if opt.quality_metrics == 'true':
-                    run.write_json('val_quality.json', {k: [v if np.isfinite(v) else None for v in vs] for k, vs in p2p.val_quality.items()})
-                    run.write_json('test_quality.json', summary(p2p.evaluate(test)))
-                    if p2p._ema_active():
-                        run.write_json('val_quality_ema.json', {k: [v if np.isfinite(v) else None for v in vs]
-                                                                for k, vs in p2p.val_quality_ema.items()})
-                        with p2p.generator_ema.averaged():
-                            run.write_json('test_quality_ema.json', summary(p2p.evaluate(test)))
-                final = run.dir('final_test_imgs', fresh=True)
-                for k, (inp, tar) in enumerate(test.unbatch()):
-                    p2p.generate_images(p2p.generator, inp[None], tar[None], os.path.join(final, f"img{k}.png"))
-                run.write_json('train_metrics.json', train_metrics)
-                run.write_json('val_metrics.json', val_metrics)
-                if p2p.lr_schedule is not None:
-                    run.write_json('learning_rate.json', p2p.learning_rates)
-                plot_loss_curves(train_metrics, val_metrics, 'Pix2Pix', os.path.join(run.root, 'figs'))
-                if info.world > 1:
-                    print(f"data-parallel run: {info.world} ranks, replicas in sync.")
-        print("Done.")
-    except BaseException:
-        try:
-            run.close()
-        finally:
-            ddp.shutdown(info, failed=True)  # no barrier on the way out of an exception: the peers are inside other collectives
-        raise
-    run.close()
-    ddp.shutdown(info)
+    training (runner.drive)."""
+    drive(opt, Pix2Pix, 'Pix2Pix', strict_logs=True, max_to_keep=1, predictor='generator', quality_logs=_write_quality_logs,
+          checkpoint_names=('generator_optimizer', 'discriminator_optimizer', 'generator', 'discriminator'))
 
 
 if __name__ == '__main__':

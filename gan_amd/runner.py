@@ -9,6 +9,7 @@ epoch (the reference pulls `.numpy()` on every loss of every step, pix2pix.py:27
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import os
 import sys
@@ -17,6 +18,9 @@ from datetime import datetime
 
 import numpy as np
 import torch
+
+from . import ddp
+from .checkpoint import Checkpoint, CheckpointManager, latest_checkpoint
 
 
 class Run:
@@ -82,6 +86,64 @@ def check_lr_decay_flags(parser, args) -> None:
         parser.error(f"--lr-decay-epochs {args.lr_decay_epochs} is more than --epochs {args.epochs}")
     if not 0.0 <= args.lr_end_factor <= 1.0:
         parser.error(f"--lr-end-factor {args.lr_end_factor} is outside [0, 1]")
+
+
+def add_common_flags(parser, argv, generator: str, networks: str) -> None:
+    """The flags both drivers take: the reference's common ones (pix2pix.py:341-377, cycle_gan.py:379-414) and this project's.
+    argv: --epochs is required with --train, --weights with --predict.  generator / networks: the model's nouns for the help
+    texts ('the generator' / 'the two generators', 'generator and discriminator' / 'generators and discriminators')."""
+    parser.add_argument('--output', type=str, help='path to output results', required=True)
+    parser.add_argument('--img-size', type=int, default=256, help='image size h,w')
+    parser.add_argument('--batch-size', type=int, default=1, help='batch size per replica')
+    parser.add_argument('--buffer-size', type=int, default=99999, help='buffer size')
+    parser.add_argument('--channels', type=str, default='1', choices=['1', '3'], help='number of color channels to read in and output')
+    parser.add_argument('--logging', type=str, default='true', choices=['true', 'false'], help='turn on/off script logging, e.g. for CLI debugging')
+    parser.add_argument('--seed', type=int, default=123, help='seed value for random number generator')
+    group = parser.add_mutually_exclusive_group(required=True)
+    group.add_argument('--train', action='store_true', help='train model using data')
+    group.add_argument('--predict', action='store_true', help='use pretrained weights to make predictions on data')
+    parser.add_argument('--save-weights', type=str, default='true', choices=['true', 'false'], help='save model checkpoints and weights')
+    parser.add_argument('--epochs', type=int, default=5, help='number of epochs to train', required='--train' in argv)
+    parser.add_argument('--validation-size', type=float, default=0.1, help='validation set size as share of number of training images')
+    parser.add_argument('--test-img', type=int, default=5, help='number of test images to sample')
+    parser.add_argument('--learning-rate', type=float, default=2e-4, help=f'learning rate for Adam optimizer for {networks}')
+    parser.add_argument('--beta-1', type=float, default=0.5, help=f'exponential decay rate for 1st moment of Adam optimizer for {networks}')
+    parser.add_argument('--beta-2', type=float, default=0.999, help=f'exponential decay rate for 2st moment of Adam optimizer for {networks}')
+    parser.add_argument('--weights', type=str, help='path to pretrained model weights for prediction', required='--predict' in argv)
+    parser.add_argument('--dtype', type=str, default='bf16', choices=['bf16', 'f16', 'f32'], help='MI355X compute/storage dtype (f32 = exact parity path)')
+    parser.add_argument('--gan-loss', type=str, default='bce', choices=['bce', 'lsgan'],
+                        help="adversarial loss on the discriminator logits: 'bce' = sigmoid cross-entropy (the reference); "
+                             "'lsgan' = least squares, mean((logit - target)^2)")
+    parser.add_argument('--predict-training', type=str, default='true', choices=['true', 'false'],
+                        help="--predict only: 'true' = the reference's generator(x, training=True) at batch 1 (batch statistics, "
+                             "dropout); 'false' = Keras inference mode (moving statistics, no dropout) in batches of --batch-size")
+    parser.add_argument('--data-cache', type=str, default='host', choices=['host', 'device'],
+                        help="--train: 'host' decodes and augments every image on the CPU in every epoch; 'device' decodes each file once, "
+                             "keeps the uint8 images in GPU memory and builds every batch there")
+    parser.add_argument('--data-cache-gb', type=float, default=64, help='--data-cache device: most GiB of decoded images to keep per GPU')
+    parser.add_argument('--ema-decay', type=float, default=0.0,
+                        help=f'--train: keep an exponential moving average of the weights of {generator} with this decay, updated on the '
+                             'GPU after every step and saved with the checkpoint (0 = off; e.g. 0.999)')
+    parser.add_argument('--ema-warmup', type=str, default='true', choices=['true', 'false'],
+                        help="--ema-decay: 'true' = decay min(ema-decay, (1 + step) / (10 + step)), so that a young average follows the weights")
+    parser.add_argument('--predict-weights', type=str, default='raw', choices=['raw', 'ema'],
+                        help="--predict: 'raw' = the checkpoint's generator weights; 'ema' = its averaged weights (a run with --ema-decay)")
+    add_lr_decay_flags(parser)
+    parser.add_argument('--device', type=str, default='cuda:0')
+    parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
+                        help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')
+    parser.add_argument('--wire', type=str, default='bf16', choices=['bf16', 'f32'], help='gradient all-reduce wire format')
+    parser.add_argument('--exchange', type=str, default='allreduce', choices=['allreduce', 'rs_ag'],
+                        help='gradient exchange: one all-reduce per bucket, or fp32 reduce-scatter + all-gather in the wire format')
+
+
+def check_common_flags(parser, args) -> None:
+    if not 0.0 <= args.ema_decay < 1.0:
+        parser.error(f"--ema-decay {args.ema_decay} is outside [0, 1)")
+    check_lr_decay_flags(parser, args)
+    assert (args.img_size == 256) or (args.img_size == 512), "img-size currently only supported for 256 x 256 or 512 x 512 pixels!"
+    assert (args.validation_size > 0.0 and args.validation_size <= 0.3), "validation size is a proportion and bounded between 0-0.3!"
+    assert (args.test_img >= 1), "test-img is an integer and must be >=1!"
 
 
 def lr_schedule_for(config, steps_per_epoch: int):
@@ -172,3 +234,67 @@ def run_epochs(epochs: int, keys, train_batches, val_batches, step, on_checkpoin
               f"val {headline[0]}: {hist[1][headline[0]][-1]:.2f}, {headline[1]}: {hist[1][headline[1]][-1]:.2f}"
               + (f"\n{extra}" if extra else "") + "\n", flush=True)
     return hist
+
+
+def drive(opt, model_class, name: str, *, strict_logs: bool, max_to_keep: int, checkpoint_names, predictor: str, quality_logs=None):
+    """What `main(opt)` of both drivers does.  One GPU, or under `torchrun --nproc-per-node N` data-parallel training: the process
+    group is joined before the first GPU call, rank r owns cuda:r, the training / validation file lists are sharded by rank after the
+    seeded split, and rank 0 alone owns the run directory (logs, checkpoints, figures).
+    name: the model's name in the figures; checkpoint_names: attributes of the model that make up a checkpoint, in the reference's
+    order; predictor: the attribute of the generator that draws the final test images; quality_logs(model, run, test): more
+    files under logs/ after training, written before the final images (Pix2Pix's image-quality metrics)."""
+    info = ddp.init_from_env(opt.device, opt.dist_backend)
+    opt.device = info.device or opt.device
+    run = Run(opt.output, log_to_file=opt.logging == 'true' and info.is_main, strict_logs=strict_logs, writer=info.is_main)
+    try:
+        model = model_class(vars(opt))
+        if opt.train:
+            model.enable_data_parallel(info, opt.wire, opt.exchange)
+        objects = {n: getattr(model, n) for n in checkpoint_names}
+        # after the generators: restore runs in this order, and an average that finds no weights of its own starts over from theirs
+        objects.update({avg.model.obj_name + '_ema': avg for avg in model.averages})
+        checkpoint = Checkpoint(**objects)
+        run.write_json('config.json', model.config)
+        if opt.predict:
+            if info.is_main:
+                dataset = model.image_pipeline(predict=True)[0]
+                checkpoint.restore(latest_checkpoint(opt.weights))
+                weights = contextlib.nullcontext()
+                if opt.predict_weights == 'ema':
+                    if not model.averages[0].loaded:
+                        raise SystemExit(f"--predict-weights ema: checkpoint holds no averaged weights ({opt.weights}); "
+                                         "train with --ema-decay")
+                    weights = model.averages[0].averaged()
+                with weights:
+                    metrics = model.predict(dataset, run.root)
+                if metrics is not None:
+                    from .quality import summary
+                    run.write_json('prediction_metrics.json', summary(metrics))
+        else:
+            *train_val, test = model.image_pipeline(predict=False)
+            manager = (CheckpointManager(checkpoint, os.path.join(run.root, 'training_checkpoints'), max_to_keep=max_to_keep)
+                       if opt.save_weights == 'true' and info.is_main else None)
+            train_metrics, val_metrics = model.fit(*train_val, test, run.root, checkpoint_manager=manager)
+            ddp.assert_replicas_in_sync([m.net.params for m in model.networks()], info)
+            if info.is_main:
+                if quality_logs is not None:
+                    quality_logs(model, run, test)
+                final = run.dir('final_test_imgs', fresh=True)
+                for k, example in enumerate(test.unbatch()):
+                    model.generate_images(getattr(model, predictor), *(a[None] for a in example), os.path.join(final, f"img{k}.png"))
+                run.write_json('train_metrics.json', train_metrics)
+                run.write_json('val_metrics.json', val_metrics)
+                if model.lr_schedule is not None:
+                    run.write_json('learning_rate.json', model.learning_rates)
+                plot_loss_curves(train_metrics, val_metrics, name, os.path.join(run.root, 'figs'))
+                if info.world > 1:
+                    print(f"data-parallel run: {info.world} ranks, replicas in sync.")
+        print("Done.")
+    except BaseException:
+        try:
+            run.close()
+        finally:
+            ddp.shutdown(info, failed=True)  # no barrier on the way out of an exception: the peers are inside other collectives
+        raise
+    run.close()
+    ddp.shutdown(info)
