@@ -136,6 +136,11 @@ class GanTileBlendDesc(_Desc):
                 ("accumulate", C.c_int32)]
 
 
+class GanPoolDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("src", GanTensor), ("dst", GanTensor), ("pool", C.c_void_p),
+                ("capacity", C.c_int32), ("stream_id", C.c_uint32), ("seed", C.c_uint64), ("state", C.c_void_p)]
+
+
 class GanLrSchedule(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("lr", C.c_float), ("end_factor", C.c_float), ("decay_start", C.c_int32),
                 ("decay_end", C.c_int32)]
@@ -202,6 +207,7 @@ SYMBOLS = {
                                          C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]),
     "gan_unpack": (C.c_int, [C.c_int32, C.POINTER(GanTensor), C.c_void_p, C.c_void_p]),
     "gan_copy_view": (C.c_int, [C.c_int32, C.POINTER(GanTensor), C.POINTER(GanTensor), C.c_void_p]),
+    "gan_pool_exchange": (C.c_int, [C.POINTER(GanPoolDesc), C.c_void_p]),
     "gan_bias_grad": (C.c_int, [C.c_int32, C.POINTER(GanTensor), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gan_grad_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gan_grad_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),

@@ -180,13 +180,16 @@ class AdamConfig:
 
 def _step_state(ctx, st):
     """Device state a warm-up pass of capture() advances besides weights and Adam moments: the fp16 loss-scale state and the
-    per-call dropout draw counters (every new batch size captures a new step: without this each capture would move them)."""
+    per-call dropout draw counters (every new batch size captures a new step: without this each capture would move them), and
+    the image pools of a CycleGAN step, state and contents."""
     ts = [ctx.ls] if ctx.ls is not None else []
     ts += [net.params.lr_now for net in st.nets() if net.params.lr_now is not None]       # (the rate a scheduled update reports)
     for call in vars(st).values():
         md = getattr(call, 'mask_draws', None)
         if isinstance(md, torch.Tensor):
             ts.append(md)
+    for pool in getattr(st, 'pools', None) or ():
+        ts += pool.tensors()
     return [(t, t.clone()) for t in ts]
 
 
@@ -200,7 +203,8 @@ class GAN(ABC):
         self.config = config
         self.ctx = Ctx(config.get('device', 'cuda:0'), config.get('dtype', 'bf16'),
                        workspace_mb=workspace_mb_for(int(config.get('batch_size', 1)), int(config.get('img_size', 256)),
-                                                     int(config.get('channels', 1))))
+                                                     int(config.get('channels', 1)),
+                                                     calls=3 if int(config.get('pool_size') or 0) > 0 else 2))
         self.loss_obj = self.loss_object()
 
     # ---- image helpers (base_gan.py:26-61) -------------------------------------------------------

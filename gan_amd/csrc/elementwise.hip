@@ -1084,3 +1084,109 @@ int gan_patchgan_losses_lsq(const float* real_logits, const float* fake_logits, 
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// image history pool (include/gan_amd.h, gan_pool_exchange)
+// ------------------------------------------------------------------------------------------------
+// A thread owns up to POOL_UNITS positions of an image (a workgroup stride apart) in EVERY image of the batch and in EVERY pool
+// slot: it walks the batch in order and does fill / swap / keep for its positions, so two images of one batch that pick the same
+// slot see each other exactly as the sequential loop says - no two threads ever touch the same pool address.  (One workgroup per
+// image would race an image's read of pool[j] against another image's write of it.)  The decisions depend on (state, b) alone:
+// every thread recomputes them, one hash per image.  U is the unit moved: 16 bytes where all three sides are dense runs, else one
+// element that is placed by (pixel, channel) in the pitched views.  state = {stored, launches, ticket}: read by every block before
+// it takes its ticket, advanced once by the last ticket holder (the hand-over of dropout_multi_kernel's `draws`).
+constexpr int POOL_UNITS = 4;
+struct PoolArgs {
+  const void* src; void* dst; void* pool; int32_t* state;
+  uint64_t seed; size_t simg, dimg;        // units between consecutive images of src / dst
+  uint32_t sid, units;                     // units of one image (= of one pool slot)
+  int B, P, C, spitch, dpitch;
+};
+template <typename U, bool DENSE>
+__global__ __launch_bounds__(256) void pool_exchange_kernel(const PoolArgs a) {
+  const int stored0 = min(max(a.state[0], 0), a.P);
+  const uint32_t launches = (uint32_t)a.state[1];
+  const uint64_t key = mix64(a.seed ^ ((uint64_t)launches << 32) ^ a.sid);
+  uint32_t so[POOL_UNITS], dof[POOL_UNITS], po[POOL_UNITS];
+  bool live[POOL_UNITS];
+#pragma unroll
+  for (int e = 0; e < POOL_UNITS; ++e) {
+    const uint32_t u = blockIdx.x * (256u * POOL_UNITS) + e * 256u + threadIdx.x;
+    live[e] = u < a.units;
+    po[e] = u;
+    if (DENSE) {
+      so[e] = dof[e] = u;
+    } else {
+      const uint32_t pix = a.C == 1 ? u : u / (uint32_t)a.C, ch = a.C == 1 ? 0u : u - pix * (uint32_t)a.C;
+      so[e] = pix * (uint32_t)a.spitch + ch;
+      dof[e] = pix * (uint32_t)a.dpitch + ch;
+    }
+  }
+  int stored = stored0;
+  for (int b = 0; b < a.B; ++b) {
+    const uint64_t h = mix64(key ^ (uint64_t)b);
+    int j = -1;                 // the slot that takes img[b]; -1: keep
+    bool take = false;          // out[b] comes from the slot (swap), not from img[b]
+    if (stored < a.P) {
+      j = stored++;
+    } else if (h >> 63) {
+      j = (int)(((h & 0xffffffffull) * (uint64_t)a.P) >> 32);
+      take = true;
+    }
+    const U* s = (const U*)a.src + (size_t)b * a.simg;
+    U* d = (U*)a.dst + (size_t)b * a.dimg;
+    U* p = (U*)a.pool + (size_t)(j < 0 ? 0 : j) * a.units;
+#pragma unroll
+    for (int e = 0; e < POOL_UNITS; ++e) {
+      if (!live[e]) continue;
+      const U v = s[so[e]];
+      if (j < 0) {
+        d[dof[e]] = v;
+      } else {
+        d[dof[e]] = take ? p[po[e]] : v;
+        p[po[e]] = v;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = atomicAdd(&a.state[2], 1);
+    if (t == (int)gridDim.x - 1) {
+      a.state[2] = 0;
+      a.state[0] = (int32_t)min((long long)a.P, (long long)stored0 + a.B);
+      a.state[1] = (int32_t)(launches + 1u);
+    }
+  }
+}
+
+extern "C" int gan_pool_exchange(const GanPoolDesc* d, gan_stream_t stream) {
+  if (!d || d->struct_size != sizeof(GanPoolDesc)) return GAN_E_ARG;
+  if (!gan_dtype_ok(d->dtype) || !d->src.ptr || !d->dst.ptr || !d->pool || !d->state || d->capacity < 1) return GAN_E_ARG;
+  const GanTensor &s = d->src, &t = d->dst;
+  if (s.n < 1 || s.h < 1 || s.w < 1 || s.c < 1 || s.pitch < s.c || t.pitch < t.c) return GAN_E_ARG;
+  if (s.n != t.n || s.h != t.h || s.w != t.w || s.c != t.c) return GAN_E_ARG;
+  const size_t es = d->dtype == GAN_F32 ? 4 : 2;
+  if ((((uintptr_t)s.ptr | (uintptr_t)t.ptr | (uintptr_t)d->pool) & (es - 1)) || ((uintptr_t)d->state & 3)) return GAN_E_ARG;
+  const long long pixels = (long long)s.h * s.w;
+  if (pixels * (s.pitch > t.pitch ? s.pitch : t.pitch) >= 0x7fffffffLL) return GAN_E_SHAPE;      // 32-bit offsets inside an image
+  PoolArgs a;
+  a.src = s.ptr; a.dst = t.ptr; a.pool = d->pool; a.state = d->state; a.seed = d->seed; a.sid = d->stream_id;
+  a.B = s.n; a.P = d->capacity; a.C = s.c; a.spitch = s.pitch; a.dpitch = t.pitch;
+  const size_t image_bytes = (size_t)pixels * s.c * es;
+  const bool dense = s.pitch == s.c && t.pitch == t.c && image_bytes % 16 == 0 &&
+                     !(((uintptr_t)s.ptr | (uintptr_t)t.ptr | (uintptr_t)d->pool) & 15);
+  hipStream_t st = (hipStream_t)stream;
+  if (dense) {
+    a.units = (uint32_t)(image_bytes / 16); a.simg = a.dimg = a.units;
+    GAN_LAUNCH((pool_exchange_kernel<uint4, true>), dim3((a.units + 256 * POOL_UNITS - 1) / (256 * POOL_UNITS)), dim3(256), 0, st, a);
+  } else {
+    a.units = (uint32_t)(pixels * s.c); a.simg = (size_t)pixels * s.pitch; a.dimg = (size_t)pixels * t.pitch;
+    const dim3 grid((a.units + 256 * POOL_UNITS - 1) / (256 * POOL_UNITS));
+    if (es == 4)
+      GAN_LAUNCH((pool_exchange_kernel<uint32_t, false>), grid, dim3(256), 0, st, a);
+    else
+      GAN_LAUNCH((pool_exchange_kernel<uint16_t, false>), grid, dim3(256), 0, st, a);
+  }
+  GAN_CHECK_LAUNCH();
+  return 0;
+}

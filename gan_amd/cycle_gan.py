@@ -14,6 +14,7 @@ import torch
 from . import data as D
 from . import ddp
 from .base_gan import GAN
+from .pool import STREAM_X, STREAM_Y, ImagePool
 from .steps import CycleGANStep
 from .runner import add_common_flags, check_common_flags, drive, save_panels
 from .utils import cyclegan_losses
@@ -34,6 +35,13 @@ class CycleGAN(GAN):
         self.generator_g_optimizer, self.generator_f_optimizer = mk(self.generator_g), mk(self.generator_f)
         self.discriminator_x_optimizer, self.discriminator_y_optimizer = mk(self.discriminator_x), mk(self.discriminator_y)
         self.generator_g_ema, self.generator_f_ema = self._init_trainer(averaged=(self.generator_g, self.generator_f))
+        # image history pools of the two discriminators (--pool-size): the model's, shared by its training steps
+        self.pools = None
+        pool_size = int(self.config.get('pool_size') or 0)
+        if pool_size < 0:
+            raise ValueError(f"pool_size {pool_size} is negative")
+        if pool_size > 0:
+            self.pools = tuple(ImagePool(self.ctx, int(self.config['img_size']), c, pool_size, seed, sid) for sid in (STREAM_Y, STREAM_X))
 
     def networks(self):
         return (self.generator_g, self.generator_f, self.discriminator_x, self.discriminator_y)
@@ -104,7 +112,8 @@ class CycleGAN(GAN):
         return CycleGANStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
                             lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
                             seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=tuple(m.net for m in self.networks()),
-                            gan_loss=self.config.get('gan_loss', 'bce'), lr_schedule=self.lr_schedule if training else None)
+                            gan_loss=self.config.get('gan_loss', 'bce'), lr_schedule=self.lr_schedule if training else None,
+                            pools=self.pools if training else None)
 
     def train_step(self, real_x, real_y, training: bool = True):
         """-> the reference's 7 losses (cycle_gan.py:275-276) as 0-d device tensors."""
@@ -162,6 +171,13 @@ class CycleGAN(GAN):
                 k += 1
 
 
+class Options(argparse.Namespace):
+    """The parsed CycleGAN command line.  --pool-size is this model's own training option: it lives in a slot beside the flag
+    dictionary (vars(opt) stays the set of flags the two drivers have in common plus their input paths) and reaches the model's
+    config through runner.config_of."""
+    __slots__ = ('pool_size',)
+
+
 def parse_opt(argv=None):
     """Same flags / defaults / assertions as cycle_gan.py:379-414 (+ this project's: runner.add_common_flags)."""
     argv = sys.argv[1:] if argv is None else argv
@@ -170,8 +186,14 @@ def parse_opt(argv=None):
     add_common_flags(parser, argv, generator='the two generators', networks='generators and discriminators')
     parser.add_argument('--target-images', type=str, help='path to target images', required='--train' in argv)
     parser.add_argument('--lambda', type=int, default=10, help='lambda parameter value')
-    args = parser.parse_args(argv)
+    parser.add_argument('--pool-size', type=int, default=0,
+                        help='image history pool per discriminator: it is trained on a random mix of current and earlier generated '
+                             'images (Zhu et al. 2017 use 50); 0 = none, the reference\'s behaviour. The pool is training-time scratch: '
+                             'it is not written to checkpoints (there is no resume-training path)')
+    args = parser.parse_args(argv, namespace=Options())
     check_common_flags(parser, args)
+    if args.pool_size < 0:
+        parser.error(f"--pool-size {args.pool_size} is negative")
     return args
 
 

@@ -1320,9 +1320,10 @@ class DiscriminatorNet:
         self.params = ParamSet(ctx, self.spec)
         self.params.load_numpy(init_params_numpy(self.spec, seed))
 
-    def new_call(self, batch, size, calls=2, lane=0, params_lane=2):
-        """lane / params_lane: whose workspace the forward + input-gradient chain / the parameter-gradient pass use."""
-        return DiscCall(self, batch, size, calls, lane, params_lane)
+    def new_call(self, batch, size, calls=2, lane=0, params_lane=2, param_calls=None):
+        """lane / params_lane: whose workspace the forward + input-gradient chain / the parameter-gradient pass use.
+        param_calls: the first that many invocations carry the parameter gradients (DiscCall); None = all of them."""
+        return DiscCall(self, batch, size, calls, lane, params_lane, param_calls=param_calls)
 
     def folded(self):
         if self.__dict__.get('_folded') is None:
@@ -1341,13 +1342,20 @@ class DiscCall:
     """`calls` invocations of the discriminator batched along N (e.g. D(real) ++ D(fake), pix2pix.py:202-203);
     BatchNormalization statistics stay per invocation (groups = calls).  Backward pass "A" covers the whole
     batch with parameter gradients (discriminator loss); pass "B" is the input-gradient-only chain over the
-    last invocation (generator's adversarial loss through D(fake), pix2pix.py:210)."""
+    last invocation (generator's adversarial loss through D(fake), pix2pix.py:210).
+    param_calls < calls: pass A covers only the first param_calls invocations - the CycleGAN step with an image history pool lays
+    the batch out as [real ; pooled ; current] (calls=3, param_calls=2): the discriminator learns from D(real) and D(pooled), the
+    generator's gradient goes through D(current).  Statistics are per invocation (BatchNorm) or per sample
+    (InstanceNorm) either way: an invocation's arithmetic does not depend on its neighbours."""
 
     LAYERS = [('down0', 64, 2), ('down1', 128, 2), ('down2', 256, 2), ('conv', 512, 1), ('last', 1, 1)]
 
-    def __init__(self, net, B, S, calls, lane=0, params_lane=2, forward_only=False):
+    def __init__(self, net, B, S, calls, lane=0, params_lane=2, forward_only=False, param_calls=None):
         ctx, P = net.ctx, net.params
         self.net, self.ctx, self.B, self.S, self.calls = net, ctx, B, S, calls
+        self.param_calls = calls if param_calls is None else int(param_calls)
+        if not 1 <= self.param_calls <= calls:
+            raise ValueError(f"param_calls {param_calls!r}: 1 ..= calls ({calls})")
         N = B * calls
         self.N = N
         bd = _Builder(ctx, P, net.norm, lane=lane)
@@ -1493,11 +1501,12 @@ class DiscCall:
         there directly (GanWgradDesc.dw_wire); the plan's wire_direct lists those kernels."""
         key = ('A', accumulate, wire or None)
         if key not in self._cache:
-            self._cache[key] = self._chain(0, self.N, self.groups, 0, True, False, accumulate, wire=wire)
+            pc = self.param_calls
+            self._cache[key] = self._chain(0, self.B * pc, pc * self.gper, 0, True, False, accumulate, wire=wire)
         return self._cache[key]
 
     def backward_params(self, accumulate=False):
-        """Pass A: dlogits (all invocations, written by the loss kernels) -> parameter gradients."""
+        """Pass A: dlogits (the first param_calls invocations, written by the loss kernels) -> parameter gradients."""
         self.ctx.run(self.params_ops(accumulate))      # (the ops carry lane-2/3 workspaces either way)
 
     def backward_input(self, call, dst=None, c0=0):

@@ -236,6 +236,15 @@ def run_epochs(epochs: int, keys, train_batches, val_batches, step, on_checkpoin
     return hist
 
 
+def config_of(opt) -> dict:
+    """The model's config of a parsed command line.  vars(opt) holds the flags the two drivers are compared on: the common set plus
+    each driver's input paths and, for Pix2Pix, its loss and prediction modes.  An option class of a driver may carry further,
+    model-specific training options beside them as slots (cycle_gan.Options: pool_size); they reach the model - and config.json -
+    through here."""
+    own = {k: getattr(opt, k) for k in getattr(type(opt), '__slots__', ())}
+    return {**vars(opt), **own}
+
+
 def drive(opt, model_class, name: str, *, strict_logs: bool, max_to_keep: int, checkpoint_names, predictor: str, quality_logs=None):
     """What `main(opt)` of both drivers does.  One GPU, or under `torchrun --nproc-per-node N` data-parallel training: the process
     group is joined before the first GPU call, rank r owns cuda:r, the training / validation file lists are sharded by rank after the
@@ -247,7 +256,7 @@ def drive(opt, model_class, name: str, *, strict_logs: bool, max_to_keep: int, c
     opt.device = info.device or opt.device
     run = Run(opt.output, log_to_file=opt.logging == 'true' and info.is_main, strict_logs=strict_logs, writer=info.is_main)
     try:
-        model = model_class(vars(opt))
+        model = model_class(config_of(opt))
         if opt.train:
             model.enable_data_parallel(info, opt.wire, opt.exchange)
         objects = {n: getattr(model, n) for n in checkpoint_names}

@@ -613,8 +613,20 @@ class CycleGANStep(_StepBase):
     wide_wgrads = True           # ... one wgrad GEMM per layer over a generator's three invocations (host + guest call)
 
     def __init__(self, ctx: Ctx, batch, size, channels=1, lam=10.0, lr=2e-4, beta_1=0.5, beta_2=0.999,
-                 seed=123, dropout=True, nets=None, mask_stream=0, merged=True, gan_loss='bce', lr_schedule=None):
+                 seed=123, dropout=True, nets=None, mask_stream=0, merged=True, gan_loss='bce', lr_schedule=None, pools=None):
+        """pools: (pool_y, pool_x), two gan_amd.pool.ImagePool objects of the MODEL (steps of other batch sizes query the same
+        two) - the discriminators then learn from a history of generated images; None: from the current ones."""
         super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=12, gan_loss=gan_loss)     # [0..8] as below; [9] cycle term of chain B; [10] stays 0
+        if pools is not None:
+            if not merged:
+                raise ValueError("pools: only the merged schedule queries an image pool (merged=False exists for one equivalence test)")
+            pools = tuple(pools)
+            if len(pools) != 2 or any((p.size, p.channels) != (size, channels) for p in pools):
+                raise ValueError(f"pools: (pool_y, pool_x) of {size} x {size} x {channels} images")
+        self.pools = pools
+        # the discriminator's batch: [real ; fake], or with pools [real ; pooled ; current] - the parameter pass covers the first two
+        # invocations, the generator's adversarial term goes through the last one
+        self._fake_call = 2 if pools else 1
         n = 'instancenorm'                                                    # cycle_gan.py:30-33
         if nets is not None:
             self.Gg, self.Gf, self.Dx, self.Dy = nets
@@ -651,8 +663,9 @@ class CycleGANStep(_StepBase):
             self.sx, self.sy = mk(self.Gf, 4), mk(self.Gg, 5)  # same_x = G_f(x); same_y = G_g(y)
         if self.merged:
             # (own workspaces for the parameter passes: they run beside the generators' wgrad lanes)
-            self.dx = self.Dx.new_call(batch, size, calls=2, lane=2, params_lane=6)       # D_x(real_x) ++ D_x(fake_x): chain B
-            self.dy = self.Dy.new_call(batch, size, calls=2, lane=0, params_lane=4)
+            nc = self._fake_call + 1
+            self.dx = self.Dx.new_call(batch, size, calls=nc, lane=2, params_lane=6, param_calls=2)       # D_x(real_x) ++ D_x(fake_x): chain B
+            self.dy = self.Dy.new_call(batch, size, calls=nc, lane=0, params_lane=4, param_calls=2)
             if ctx.lanes:
                 self.dx._bd2.wgrad_concurrent = self.dy._bd2.wgrad_concurrent = 2
         else:
@@ -664,6 +677,14 @@ class CycleGANStep(_StepBase):
 
     def nets(self):
         return (self.Gg, self.Gf, self.Dx, self.Dy)
+
+    def capture(self, training=True):
+        """The warm-up passes query the image pools: they are left as they were found, state and contents."""
+        saved = [(t, t.clone()) for pool in self.pools or () for t in pool.tensors()]
+        replay = super().capture(training)
+        for t, v in saved:
+            t.copy_(v)
+        return replay
 
     def _prebuild_fused_adam(self):
         if self._wgrad_adam_ok() and self.merged and self.two_chains and self.early_adam and self.wide_wgrads and self._wide:
@@ -763,14 +784,20 @@ class CycleGANStep(_StepBase):
         chain_b = (lambda: torch.cuda.stream(l2)) if two else contextlib.nullcontext
         self._pack_multi([(real_x, fy.xin_view()), (real_y, sy.xin_view()), (real_y, fx.xin_view()), (real_x, sx.xin_view())])
         self._pack_multi([(real_x, dx.xin.view(0, Cc, 0, B)), (real_y, dy.xin.view(0, Cc, 0, B))])
-        rx_ptr, cnt = dx.logits_view(0); fxl_ptr, _ = dx.logits_view(1)
-        ry_ptr, _ = dy.logits_view(0); fyl_ptr, _ = dy.logits_view(1)
+        fc, pools = self._fake_call, self.pools
+        if pools and not training:
+            raise ValueError("a step with image pools is a training step (validation judges the current fakes)")
+        rx_ptr, cnt = dx.logits_view(0); fxl_ptr, _ = dx.logits_view(fc)       # generator side: D(current fakes)
+        ry_ptr, _ = dy.logits_view(0); fyl_ptr, _ = dy.logits_view(fc)
+        pxl_ptr, _ = dx.logits_view(1); pyl_ptr, _ = dy.logits_view(1)        # discriminator side: D(pooled), = D(current) without pools
         xv, yv = fy.xin_view(), sy.xin_view()                         # typed real_x / real_y
         lp = self.losses.data_ptr()
         if two:
             l2.wait_stream(main)
         gA.forward()                                                  # cycle_gan.py:220 and :228
-        self._copy(fy.out_view(), cx.xin.view(0, Cc)); self._copy(fy.out_view(), dy.xin.view(0, Cc, B, B))
+        self._copy(fy.out_view(), cx.xin.view(0, Cc)); self._copy(fy.out_view(), dy.xin.view(0, Cc, fc * B, B))
+        if pools:
+            pools[0].exchange(fy.out_view(), dy.xin.view(0, Cc, B, B))
         cx.forward()                                                  # :221
         dy.forward()                                                  # :233-234
         if two:
@@ -780,10 +807,12 @@ class CycleGANStep(_StepBase):
             self._l1(cx.out_view(), xv, 2, lam, False, lam, cx.dgen.view(0, Cc))              # cycle term of x :240
             self._l1(sy.out_view(), yv, 7, lam * 0.5, False, lam * 0.5, sy.dgen_view())       # identity :243
             self._bce(ry_ptr, cnt, 1.0, 6, 0.5, False, 0.5, dy.dlogits_ptr(0))                # disc_y_loss :247
-            self._bce(fyl_ptr, cnt, 0.0, 6, 0.5, True, 0.5, dy.dlogits_ptr(1))
+            self._bce(pyl_ptr, cnt, 0.0, 6, 0.5, True, 0.5, dy.dlogits_ptr(1))
         with chain_b():
             gB.forward()                                              # :223 and :227
-            self._copy(fx.out_view(), cy.xin.view(0, Cc)); self._copy(fx.out_view(), dx.xin.view(0, Cc, B, B))
+            self._copy(fx.out_view(), cy.xin.view(0, Cc)); self._copy(fx.out_view(), dx.xin.view(0, Cc, fc * B, B))
+            if pools:
+                pools[1].exchange(fx.out_view(), dx.xin.view(0, Cc, B, B))
             cy.forward()                                              # :224
             dx.forward()                                              # :230-231
             if two:
@@ -792,7 +821,7 @@ class CycleGANStep(_StepBase):
                 self._l1(cy.out_view(), yv, 9, lam, False, lam, cy.dgen.view(0, Cc), ws=wl)              # cycle term of y
                 self._l1(sx.out_view(), xv, 8, lam * 0.5, False, lam * 0.5, sx.dgen_view(), ws=wl)       # identity :244
                 self._bce(rx_ptr, cnt, 1.0, 5, 0.5, False, 0.5, dx.dlogits_ptr(0), ws=wb)                # disc_x_loss :246
-                self._bce(fxl_ptr, cnt, 0.0, 5, 0.5, True, 0.5, dx.dlogits_ptr(1), ws=wb)
+                self._bce(pxl_ptr, cnt, 0.0, 5, 0.5, True, 0.5, dx.dlogits_ptr(1), ws=wb)
         if not two:
             self._bce(fyl_ptr, cnt, 1.0, 0, 1.0, False, 1.0, dy.dlogits_b.t.data_ptr())      # gen_g_loss :237
             self._bce(fxl_ptr, cnt, 1.0, 1, 1.0, False, 1.0, dx.dlogits_b.t.data_ptr())      # gen_f_loss :238
@@ -802,9 +831,9 @@ class CycleGANStep(_StepBase):
             self._l1(sx.out_view(), xv, 8, lam * 0.5, False, lam * 0.5, sx.dgen_view())       # identity :244
             self._totals(False)
             self._bce(rx_ptr, cnt, 1.0, 5, 0.5, False, 0.5, dx.dlogits_ptr(0))                # disc_x_loss :246
-            self._bce(fxl_ptr, cnt, 0.0, 5, 0.5, True, 0.5, dx.dlogits_ptr(1))
+            self._bce(pxl_ptr, cnt, 0.0, 5, 0.5, True, 0.5, dx.dlogits_ptr(1))
             self._bce(ry_ptr, cnt, 1.0, 6, 0.5, False, 0.5, dy.dlogits_ptr(0))                # disc_y_loss :247
-            self._bce(fyl_ptr, cnt, 0.0, 6, 0.5, True, 0.5, dy.dlogits_ptr(1))
+            self._bce(pyl_ptr, cnt, 0.0, 6, 0.5, True, 0.5, dy.dlogits_ptr(1))
         elif not training:
             self.ctx.join(main, l2)
             self._totals(True)
@@ -853,11 +882,11 @@ class CycleGANStep(_StepBase):
                     return False
 
                 cx.backward(need_dx=True, accumulate=False, wgrads=w1)    # G_f grads (cycle_x), d/d fake_y
-                dy.backward_input(1, dst=fy.dgen_view())              # adversarial term through D_y(fake_y)
+                dy.backward_input(fc, dst=fy.dgen_view())             # adversarial term through D_y(fake_y)
                 self._copy(cx.dxin.view(0, Cc), fy.dgen_view(second=True))
                 with chain_b():
                     cy.backward(need_dx=True, accumulate=False, wgrads=w1)    # G_g grads (cycle_y), d/d fake_x
-                    dx.backward_input(1, dst=fx.dgen_view())
+                    dx.backward_input(fc, dst=fx.dgen_view())
                     self._copy(cy.dxin.view(0, Cc), fx.dgen_view(second=True))
                 ea, eb = torch.cuda.Event(), torch.cuda.Event()
                 ea.record(main); eb.record(l2)
@@ -888,9 +917,9 @@ class CycleGANStep(_StepBase):
                 return self.losses
             cx.backward(need_dx=True, accumulate=False)               # G_f grads (cycle_x), d/d fake_y
             cy.backward(need_dx=True, accumulate=False)               # G_g grads (cycle_y), d/d fake_x
-            dy.backward_input(1, dst=fy.dgen_view())                  # adversarial term through D_y(fake_y)
+            dy.backward_input(fc, dst=fy.dgen_view())                 # adversarial term through D_y(fake_y)
             self._copy(cx.dxin.view(0, Cc), fy.dgen_view(second=True))
-            dx.backward_input(1, dst=fx.dgen_view())
+            dx.backward_input(fc, dst=fx.dgen_view())
             self._copy(cy.dxin.view(0, Cc), fx.dgen_view(second=True))
             # second upstream slot of the identity halves stays zero (never written); one backward per generator covers the
             # adversarial + cycle gradient of fake_* and the identity gradient of same_*

@@ -461,6 +461,36 @@ int gan_unpack(int32_t dtype, const GanTensor* src, float* dst, gan_stream_t str
 /* typed view -> typed view (same n,h,w,c; pitches / channel offsets may differ): places the generator
  * output into the discriminator's concat input (base_gan.py:139) and routes its gradient back. */
 int gan_copy_view(int32_t dtype, const GanTensor* src, const GanTensor* dst, gan_stream_t stream);
+/* Image history pool of a discriminator (no counterpart in the reference; Zhu et al. 2017, section 4 after Shrivastava et al.:
+ * the discriminator is trained on a history of generated images).  One query takes the n = src.n current images in batch order:
+ *     for b in 0 .. n-1:   if stored < capacity:  pool[stored] = img[b]; out[b] = img[b]; stored += 1        (fill)
+ *                          elif swap(b):          j = slot(b); out[b] = pool[j]; pool[j] = img[b]              (swap)
+ *                          else:                  out[b] = img[b]                                              (keep)
+ *     key = mix64(seed ^ ((uint64)(uint32)launches << 32) ^ stream_id),  h = mix64(key ^ b)       (the dropout masks' counter hash)
+ *     swap(b) = h >> 63,   slot(b) = ((h & 0xffffffff) * capacity) >> 32
+ * `launches` is the pool's own counter, not an Adam step counter: a skipped fp16 step still advances the pool.  The sequential
+ * semantics hold exactly, also for several images of one batch that pick the same slot (a thread owns its element positions in
+ * every image and every slot).  Bits are moved, nothing is computed.  One launch; enqueue-only and capturable: the state lives on
+ * the device and advances on replay. */
+typedef struct GanPoolDesc {
+  uint32_t struct_size;
+  int32_t dtype;               /* GAN_F32 | GAN_BF16 | GAN_F16: storage of src, dst and pool */
+  GanTensor src;               /* the n current images (the generator's output view): only read */
+  GanTensor dst;               /* out: same n, h, w, c, own pitch (a slot of the discriminator's input); only the c real channels of
+                                  a pixel are written, the pad channels of a wider pitch keep what they hold */
+  void* pool;                  /* device: dense [capacity][h][w][c] of dtype; only the filled or swapped slots are written */
+  int32_t capacity;            /* >= 1 */
+  uint32_t stream_id;          /* tells the pools of one seed apart */
+  uint64_t seed;
+  int32_t* state;              /* device int32[3], zero-initialised by the caller: {stored, launches, block ticket}; every workgroup
+                                  reads it before it takes a ticket, the last ticket holder stores min(capacity, stored + n) and
+                                  launches + 1 and clears the ticket */
+} GanPoolDesc;
+/* 16-byte accesses where src, dst and pool are dense runs (pitch == c, h * w * c * element size a multiple of 16, 16-byte aligned
+ * pointers); element accesses placed by (pixel, channel) otherwise - the 8-channel-padded views with c = 1 or 3.
+ * GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype, capacity < 1, n / h / w / c of src and dst differ or are < 1, pitch < c,
+ * a pointer not aligned to its element size.  GAN_E_SHAPE: h * w * pitch of an image >= 2^31.  All found before the launch. */
+int gan_pool_exchange(const GanPoolDesc* d, gan_stream_t stream);
 /* bias gradient: dbias[c] (+)= sum over n,h,w of dy[...,c]; dy.c 8-padded, dbias has dy.c entries.
  * workspace >= gan_norm_workspace_bytes(1, dy.c, n*h*w). */
 int gan_bias_grad(int32_t dtype, const GanTensor* dy, float* dbias, int32_t accumulate, void* workspace,

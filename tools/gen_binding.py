@@ -6,7 +6,8 @@ import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CT = {'int32_t': 'C.c_int32', 'uint32_t': 'C.c_uint32', 'float': 'C.c_float', 'size_t': 'C.c_size_t', 'int64_t': 'C.c_int64'}
+CT = {'int32_t': 'C.c_int32', 'uint32_t': 'C.c_uint32', 'float': 'C.c_float', 'size_t': 'C.c_size_t', 'int64_t': 'C.c_int64',
+      'uint64_t': 'C.c_uint64'}
 
 
 def parse_structs(header=None):
