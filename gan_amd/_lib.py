@@ -130,6 +130,13 @@ class GanTileGatherDesc(_Desc):
                 ("dst", GanTensor)]
 
 
+class GanTileGatherFDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("src_dtype", C.c_int32), ("src", C.c_void_p), ("src_elems", C.c_int64),
+                ("src_pitch", C.c_int32), ("col0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32),
+                ("tile", C.c_int32), ("overlap", C.c_int32), ("t0", C.c_int32), ("n", C.c_int32), ("dst_dtype", C.c_int32),
+                ("dst", GanTensor)]
+
+
 class GanTileBlendDesc(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("tiles", GanTensor), ("image", C.c_void_p), ("h", C.c_int32),
                 ("w", C.c_int32), ("c", C.c_int32), ("tile", C.c_int32), ("overlap", C.c_int32), ("t0", C.c_int32), ("n", C.c_int32),
@@ -218,6 +225,7 @@ SYMBOLS = {
     "gan_dssim": (C.c_int, [C.POINTER(GanDssimDesc), C.c_void_p]),
     "gan_tile_grid": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gan_tile_gather_u8": (C.c_int, [C.POINTER(GanTileGatherDesc), C.c_void_p]),
+    "gan_tile_gather": (C.c_int, [C.POINTER(GanTileGatherFDesc), C.c_void_p]),
     "gan_tile_blend": (C.c_int, [C.POINTER(GanTileBlendDesc), C.c_void_p]),
     "gan_crc32c": (C.c_uint32, [C.c_uint32, C.c_void_p, C.c_size_t]),
     "gan_version": (C.c_char_p, []),

@@ -110,7 +110,11 @@ class GeneratorModel(_Model):
 
     def infer_tiled(self, src_u8, *, tile, overlap, col0=0, width=None, batch=None, fold=True):
         """Inference mode over a whole uint8 device image [H, W, C] of any size >= tile: overlapping tile x tile pieces through
-        the eval call as a batch, blended back on the device -> fp32 device tensor [H, width, C] (gan_amd/tiling.py)."""
+        the eval call as a batch, blended back on the device -> fp32 device tensor [H, width, C] (gan_amd/tiling.py).  This method
+        keeps to decoded image files: anything but uint8 is refused; a float image that is normalised already (the output of
+        another generator) goes through tiling.infer_tiled itself."""
+        if not isinstance(src_u8, torch.Tensor) or src_u8.dtype != torch.uint8:
+            raise ValueError("infer_tiled: expected a contiguous uint8 [H, W, C] tensor on the model's device")
         return tiling.infer_tiled(self, src_u8, tile=tile, overlap=overlap, col0=col0, width=width, batch=batch, fold=fold)
 
 

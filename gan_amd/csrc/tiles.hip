@@ -22,6 +22,11 @@
 // finds the covering tiles, reads them (one 16-byte load per tile for a 16-bit view of pitch 8) and writes its c floats once - no
 // atomics, no workspace.  tile_gather_kernel gives every destination pixel to one thread, which reads its c source bytes through
 // the clamped index and writes the c real channels; the pad channels of a wider pitch are not touched, as gan_pack leaves them.
+//
+// tile_gather_f_kernel (gan_tile_gather) is the same gather from a float image - the blended fp32 output of one generator as the
+// input of the next, the cycle of a CycleGAN at the source resolution - with a bit copy or one rounding in place of the table.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -78,6 +83,41 @@ __global__ __launch_bounds__(TILE_THREADS) void tile_gather_kernel(const GatherA
     T* o = dst + i * a.pitch;
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) st_f(o + ch, a.lut[a.src[min(max(at + ch, 0LL), a.src_bytes - 1)]]);
+  }
+}
+
+struct GatherFArgs {
+  const void* src;
+  long long src_elems;
+  int src_pitch, col0;         // elements / pixels
+  TileGeo g;
+  int t0, n;
+  void* dst;
+  int pitch;
+};
+
+// The float-source sibling: the same thread-per-destination-pixel index arithmetic, no table.  TS == TD moves the bits (a NaN keeps
+// its payload); otherwise TS is float and st_f rounds to nearest.
+template <typename TS, typename TD, int C>
+__global__ __launch_bounds__(TILE_THREADS) void tile_gather_f_kernel(const GatherFArgs a) {
+  const int S = a.g.tile;
+  const long long per = (long long)S * S, total = per * a.n;
+  const TS* __restrict__ src = (const TS*)a.src;
+  TD* __restrict__ dst = (TD*)a.dst;
+  for (long long i = (long long)blockIdx.x * TILE_THREADS + threadIdx.x; i < total; i += (long long)gridDim.x * TILE_THREADS) {
+    const int tl = (int)(i / per), rem = (int)(i - tl * per);
+    const int r = rem / S, x = rem - r * S;
+    const int t = a.t0 + tl, ky = t / a.g.nx, kx = t - ky * a.g.nx;
+    const int sy = axis_origin(ky, a.g.ny, a.g.h, S, a.g.stride) + r;
+    const int sx = axis_origin(kx, a.g.nx, a.g.w, S, a.g.stride) + x;
+    const long long at = (long long)sy * a.src_pitch + (long long)(a.col0 + sx) * C;
+    TD* o = dst + i * a.pitch;
+#pragma unroll
+    for (int ch = 0; ch < C; ++ch) {
+      const TS v = src[min(max(at + ch, 0LL), a.src_elems - 1)];
+      if constexpr (std::is_same<TS, TD>::value) o[ch] = v;
+      else st_f(o + ch, ld_f(&v));
+    }
   }
 }
 
@@ -163,6 +203,13 @@ template <typename T> void launch_gather(int c, const GatherArgs& a, dim3 grid, 
     GAN_LAUNCH((tile_gather_kernel<T, 3>), grid, dim3(TILE_THREADS), 0, st, a);
 }
 
+template <typename TS, typename TD> void launch_gather_f(int c, const GatherFArgs& a, dim3 grid, hipStream_t st) {
+  if (c == 1)
+    GAN_LAUNCH((tile_gather_f_kernel<TS, TD, 1>), grid, dim3(TILE_THREADS), 0, st, a);
+  else
+    GAN_LAUNCH((tile_gather_f_kernel<TS, TD, 3>), grid, dim3(TILE_THREADS), 0, st, a);
+}
+
 template <typename T> void launch_blend(int c, bool vec, const BlendArgs& a, dim3 grid, hipStream_t st) {
   if (c == 1) {
     if (vec) GAN_LAUNCH((tile_blend_kernel<T, 1, true>), grid, dim3(TILE_THREADS), 0, st, a);
@@ -204,6 +251,37 @@ extern "C" int gan_tile_gather_u8(const GanTileGatherDesc* d, gan_stream_t strea
     case GAN_F32: launch_gather<float>(d->c, a, grid, st); break;
     case GAN_BF16: launch_gather<bf16_t>(d->c, a, grid, st); break;
     default: launch_gather<f16_t>(d->c, a, grid, st); break;
+  }
+  GAN_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int gan_tile_gather(const GanTileGatherFDesc* d, gan_stream_t stream) {
+  if (!d || d->struct_size != sizeof(GanTileGatherFDesc)) return GAN_E_ARG;
+  if (!d->src || !d->dst.ptr) return GAN_E_ARG;
+  if (!gan_dtype_ok(d->src_dtype) || !gan_dtype_ok(d->dst_dtype) || (d->c != 1 && d->c != 3)) return GAN_E_ARG;
+  if (d->src_dtype != d->dst_dtype && d->src_dtype != GAN_F32) return GAN_E_ARG;      // a bit copy, or fp32 rounded once
+  GatherFArgs a;
+  const int rc = check_tiles(d->dst, d->dst_dtype, d->h, d->w, d->c, d->tile, d->overlap, d->t0, d->n, &a.g);
+  if (rc) return rc;
+  if ((uintptr_t)d->src % dtype_size(d->src_dtype)) return GAN_E_ARG;
+  // the part used lies inside a source row, and its last row inside the buffer
+  if (d->col0 < 0 || d->src_pitch < 1 || d->src_elems < 1 || ((long long)d->col0 + d->w) * d->c > d->src_pitch) return GAN_E_ARG;
+  if ((long long)(d->h - 1) * d->src_pitch + ((long long)d->col0 + d->w) * d->c > d->src_elems) return GAN_E_ARG;
+  a.src = d->src; a.src_elems = d->src_elems; a.src_pitch = d->src_pitch; a.col0 = d->col0;
+  a.t0 = d->t0; a.n = d->n; a.dst = d->dst.ptr; a.pitch = d->dst.pitch;
+  const dim3 grid(tile_blocks((long long)d->n * d->tile * d->tile));
+  hipStream_t st = (hipStream_t)stream;
+  if (d->src_dtype == GAN_F32) {
+    switch (d->dst_dtype) {
+      case GAN_F32: launch_gather_f<float, float>(d->c, a, grid, st); break;
+      case GAN_BF16: launch_gather_f<float, bf16_t>(d->c, a, grid, st); break;
+      default: launch_gather_f<float, f16_t>(d->c, a, grid, st); break;
+    }
+  } else if (d->src_dtype == GAN_BF16) {
+    launch_gather_f<bf16_t, bf16_t>(d->c, a, grid, st);
+  } else {
+    launch_gather_f<f16_t, f16_t>(d->c, a, grid, st);
   }
   GAN_CHECK_LAUNCH();
   return 0;

@@ -4,6 +4,7 @@ shared backward and four Adam updates run as one captured hipGraph (gan_amd/step
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import random
 import sys
@@ -11,12 +12,16 @@ import sys
 import numpy as np
 import torch
 
+from . import cycle_quality as Q
 from . import data as D
 from . import ddp
+from . import tiling
 from .base_gan import GAN
 from .pool import STREAM_X, STREAM_Y, ImagePool
+from .quality import QualityMeter, summary
 from .steps import CycleGANStep
-from .runner import add_common_flags, check_common_flags, drive, save_panels
+from .runner import (add_common_flags, add_prediction_flags, check_common_flags, check_prediction_flags, drive, finite_lists,
+                     save_panels, tile_overlap_of)
 from .utils import cyclegan_losses
 
 
@@ -141,41 +146,134 @@ class CycleGAN(GAN):
         finally:
             ix.close(); iy.close()
 
+    def _averaged(self):
+        """Both generators on their averaged weights (--ema-decay) for the length of the block."""
+        stack = contextlib.ExitStack()
+        for avg in self.averages:
+            stack.enter_context(avg.averaged())
+        return stack
+
+    def _fold(self):
+        self.generator_g.fold()
+        self.generator_f.fold()
+
+    def _evaluate_into(self, meter, ds_x, ds_y=None):
+        """Enqueue the cycles and the metrics of every batch (no host sync).  ds_y: zipped with ds_x as the validation pass is."""
+        self._fold()        # once: the weights stand still during the pass
+        with D.uncounted_passes(ds_x, ds_y):        # the later epochs draw the orders they draw without this pass
+            if ds_y is None:
+                for (x,) in ds_x:
+                    meter.add(Q.cycle_quality(self, x))
+            else:
+                for x, y in self._zipped(ds_x, ds_y):
+                    meter.add(Q.cycle_quality(self, x, y))
+
+    def evaluate(self, ds_x, ds_y=None):
+        """Cycle-consistency quality over a dataset (gan_amd/cycle_quality.py), as Pix2Pix.evaluate:
+        -> {'cycle_x_ssim': [...], 'cycle_x_psnr': [...], 'cycle_x_mae': [...], 'identity_x_ssim': [...], ...}, one entry per image
+        in the order the sets yield them (file order unless a set shuffles): F(G(x)) and F(x) against x; with ds_y also the cycle_y_* / identity_y_* of G(F(y)) and G(y) against y, over
+        the zip of the two sets.  Inference mode, in the datasets' batches.  An inference forward writes no state: training is
+        unchanged by it, bit for bit."""
+        meter = QualityMeter()
+        self._evaluate_into(meter, ds_x, ds_y)
+        return meter.drain(Q.keys(Q.GROUPS_X if ds_y is None else Q.GROUPS_X + Q.GROUPS_Y))
+
     def fit(self, train_X, train_Y, val_X, val_Y, test, output_path: str, checkpoint_manager=None):
         print("\nTraining...\n", flush=True)
         it = iter(test)
         example = next(it)[0]
         it.close()
+        names = Q.keys()
+        self.val_quality = {k: [] for k in names}
+        self.val_quality_ema = {k: [] for k in names}
+        after_epoch = None
+        if str(self.config.get('quality_metrics', 'false')) == 'true':
+            def val_pass(into):         # the zipped validation sets in inference mode; epoch means over all ranks' images, as the losses
+                meter = QualityMeter()
+                self._evaluate_into(meter, val_X, val_Y)
+                mean = ddp.mean_over_ranks(*meter.sums(), self.dist)
+                vals = mean.cpu().tolist() if mean is not None else [float('nan')] * len(names)
+                for k, v in zip(names, vals):
+                    into[k].append(v)
+                v = dict(zip(names, vals))
+                return (f"val cycle x SSIM: {v['cycle_x_ssim']:.4f}, PSNR: {v['cycle_x_psnr']:.2f} dB, MAE: {v['cycle_x_mae']:.4f}; "
+                        f"cycle y SSIM: {v['cycle_y_ssim']:.4f}, PSNR: {v['cycle_y_psnr']:.2f} dB, MAE: {v['cycle_y_mae']:.4f}")
+
+            def after_epoch(epoch):
+                line = val_pass(self.val_quality)
+                if self._ema_active():  # the same pass on the averaged weights
+                    with self._averaged():
+                        line += " | averaged weights: " + val_pass(self.val_quality_ema)
+                return line
         # (the zip of the two unpaired sets stops at the shorter one: that many updates per epoch)
         return self._fit(output_path, checkpoint_manager, cyclegan_losses(), lambda: self._zipped(train_X, train_Y),
                          lambda: self._zipped(val_X, val_Y), min(len(train_X), len(train_Y)),
                          ('Total X->Y Generator Loss', 'Discriminator Y Loss'),
-                         lambda path: self.generate_images(self.generator_g, example[:1], path))
+                         lambda path: self.generate_images(self.generator_g, example[:1], path), after_epoch)
 
     def predict(self, predict_ds, output_path: str):
         """As Pix2Pix.predict: config['predict_training'] 'false' runs generator_g in inference mode (InstanceNorm has no
-        inference-time state: no dropout is the only difference) in batches of config['batch_size'] images."""
+        inference-time state: no dropout is the only difference) in batches of config['batch_size'] images.
+        config['predict_resolution'] 'native' (inference mode only): every image at its source size, tiled (_predict_native).
+        config['quality_metrics'] 'true' (inference mode only: with dropout the cycle is not a deterministic measurement): -> the
+        cycle-consistency metrics per image in file order (cycle_x_* and, at img_size, identity_x_*); otherwise None."""
         plot_path = os.path.join(output_path, 'prediction_images')
         os.makedirs(plot_path)
+        metrics = str(self.config.get('quality_metrics', 'false')) == 'true'
+        gray = self.config['channels'] == '1'
         if str(self.config.get('predict_training', 'true')) == 'true':
+            if metrics or str(self.config.get('predict_resolution', 'resized')) == 'native':
+                raise ValueError("quality_metrics / predict_resolution native need predict_training 'false': with dropout the cycle "
+                                 "is not a deterministic measurement, and tiles are only meaningful in inference mode")
             for k, (img,) in enumerate(predict_ds.unbatch()):
                 self.generate_images(self.generator_g, img[None], os.path.join(plot_path, f"img{k}.png"))
-            return
-        self.generator_g.fold()
+            return None
+        meter = QualityMeter() if metrics else None
+        self._fold()
+        if str(self.config.get('predict_resolution', 'resized')) == 'native':
+            self._predict_native(predict_ds.files, plot_path, meter, gray)
+            return meter.drain(Q.keys(('cycle_x',))) if metrics else None
         k = 0
         for chunk in D.chunked(predict_ds.unbatch(), int(self.config['batch_size'])):
-            pred = self.generator_g.infer(np.stack([img for (img,) in chunk]), fold=False).cpu().numpy()
+            x = np.stack([img for (img,) in chunk])
+            if metrics:             # the cycle starts with this very prediction: it is read from generator_g's eval call afterwards
+                meter.add(Q.cycle_quality(self, x))
+                pred = self.generator_g.eval_call(*x.shape[:2]).output_f32().cpu().numpy()
+            else:
+                pred = self.generator_g.infer(x, fold=False).cpu().numpy()
             for (img,), p in zip(chunk, pred):
-                save_panels(os.path.join(plot_path, f"img{k}.png"), [('Input Image', img), ('Predicted Image', p)],
-                            gray=self.config['channels'] == '1')
+                save_panels(os.path.join(plot_path, f"img{k}.png"), [('Input Image', img), ('Predicted Image', p)], gray=gray)
                 k += 1
+        return meter.drain(Q.keys(Q.GROUPS_X)) if metrics else None
+
+    def _predict_native(self, files, plot_path, meter, gray):
+        """Prediction at the source resolution (DESIGN.md sections 13 and 19): each file is decoded once and uploaded once as
+        uint8, goes through generator_g as overlapping img_size tiles and the two panels are written at the source size.  With a
+        meter the prediction comes from cycle_quality_tiled, which sends it on through generator_f and compares the cycled image
+        with the normalised source, all on the device."""
+        S, c, V = int(self.config['img_size']), int(self.config['channels']), tile_overlap_of(self.config)
+        for k, f in enumerate(files):
+            img = D.decode(f, c)
+            H, W = img.shape[:2]
+            if H < S or W < S:
+                raise ValueError(f"{f}: the image is {H} x {W}, smaller than --img-size {S}; --predict-resolution native does "
+                                 "not pad (use --predict-resolution resized)")
+            src = torch.from_numpy(img.copy()).to(self.ctx.device)      # the one upload
+            if meter is not None:
+                rows, pred, _ = Q.cycle_quality_tiled(self, src, tile=S, overlap=V)
+                meter.add(rows)
+            else:
+                pred = tiling.infer_tiled(self.generator_g, src, tile=S, overlap=V, fold=False)
+            panels = [('Input Image', D.normalize(img.astype(np.float32))), ('Predicted Image', pred.cpu().numpy())]
+            save_panels(os.path.join(plot_path, f"img{k}.png"), panels, gray=gray)
 
 
 class Options(argparse.Namespace):
-    """The parsed CycleGAN command line.  --pool-size is this model's own training option: it lives in a slot beside the flag
-    dictionary (vars(opt) stays the set of flags the two drivers have in common plus their input paths) and reaches the model's
-    config through runner.config_of."""
-    __slots__ = ('pool_size',)
+    """The parsed CycleGAN command line.  --pool-size and the prediction / measurement flags (--quality-metrics,
+    --predict-resolution, --tile-overlap) are this driver's own options: they live in slots beside the flag dictionary (vars(opt)
+    stays the set of flags the two drivers have in common plus their input paths) and reach the model's config through
+    runner.config_of."""
+    __slots__ = ('pool_size', 'quality_metrics', 'predict_resolution', 'tile_overlap')
 
 
 def parse_opt(argv=None):
@@ -190,17 +288,38 @@ def parse_opt(argv=None):
                         help='image history pool per discriminator: it is trained on a random mix of current and earlier generated '
                              'images (Zhu et al. 2017 use 50); 0 = none, the reference\'s behaviour. The pool is training-time scratch: '
                              'it is not written to checkpoints (there is no resume-training path)')
+    add_prediction_flags(parser, image='image', resized=' (the reference)',
+                         metrics="cycle-consistency quality, computed on the GPU in inference mode (SSIM as tf.image.ssim, PSNR, MAE of "
+                                 "F(G(x)) and F(x) against x, G(F(y)) and G(y) against y): --train writes logs/val_quality.json (per "
+                                 "epoch) and logs/test_quality.json, --predict (needs --predict-training false) writes "
+                                 "logs/prediction_metrics.json")
     args = parser.parse_args(argv, namespace=Options())
     check_common_flags(parser, args)
     if args.pool_size < 0:
         parser.error(f"--pool-size {args.pool_size} is negative")
+    check_prediction_flags(parser, args)
+    if args.quality_metrics == 'true' and args.predict and args.predict_training == 'true':
+        parser.error("--quality-metrics true with --predict requires --predict-training false: with --predict-training true the "
+                     "generators run with dropout, and the cycle F(G(x)) is then not a deterministic measurement")
     return args
+
+
+def _write_quality_logs(gan, run, test):
+    """--quality-metrics true: the per-epoch validation metrics and those of the test set (X only), also on the averaged weights."""
+    if str(gan.config.get('quality_metrics', 'false')) != 'true':
+        return
+    run.write_json('val_quality.json', finite_lists(gan.val_quality))
+    run.write_json('test_quality.json', summary(gan.evaluate(test)))
+    if gan._ema_active():
+        run.write_json('val_quality_ema.json', finite_lists(gan.val_quality_ema))
+        with gan._averaged():
+            run.write_json('test_quality_ema.json', summary(gan.evaluate(test)))
 
 
 def main(opt):
     """One GPU, or `torchrun --nproc-per-node N cycle_gan.py --train ...` (data parallel): runner.drive."""
     names = ('generator_g', 'generator_f', 'discriminator_x', 'discriminator_y')        # object names of cycle_gan.py:437-444
-    drive(opt, CycleGAN, 'CycleGAN', strict_logs=False, max_to_keep=3, predictor='generator_g',
+    drive(opt, CycleGAN, 'CycleGAN', strict_logs=False, max_to_keep=3, predictor='generator_g', quality_logs=_write_quality_logs,
           checkpoint_names=names + tuple(n + '_optimizer' for n in names))
 
 

@@ -5,6 +5,7 @@ background thread decodes ahead (CPU only), the consuming thread pins and upload
 after the decode: DeviceDataset keeps the uint8 images in HBM, DeviceBatches builds the same batches with gan_augment_u8."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import queue
@@ -160,6 +161,21 @@ class Batches:
     def unbatch(self):
         for f in self.files:
             yield self.make_example(f)
+
+
+@contextlib.contextmanager
+def uncounted_passes(*sets):
+    """Passes over `sets` inside the block do not count.  A shuffled Batches / DeviceBatches counts its passes to draw the order of
+    the next one; a measurement that walks a set once more (CycleGAN.evaluate between two epochs) must not move the orders of the
+    later epochs.  Inside, successive passes still draw successive orders, starting from the one that is due; on the way out the
+    counters are back.  Anything else among `sets` (a list of batches, a generator, None) has no order to keep and is left alone."""
+    counted = [d for d in sets if isinstance(d, (Batches, DeviceBatches))]
+    epochs = [d.epoch for d in counted]
+    try:
+        yield
+    finally:
+        for d, epoch in zip(counted, epochs):
+            d.epoch = epoch
 
 
 def chunked(items, n):

@@ -16,7 +16,8 @@ from . import tiling
 from .base_gan import GAN
 from .quality import QualityMeter, image_quality, summary
 from .steps import Pix2PixStep
-from .runner import add_common_flags, check_common_flags, drive, save_panels
+from .runner import (add_common_flags, add_prediction_flags, check_common_flags, check_prediction_flags, drive, finite_lists,
+                     save_panels, tile_overlap_of)
 from .utils import pix2pix_losses
 
 
@@ -216,9 +217,7 @@ class Pix2Pix(GAN):
         and target are its two halves by column offset, the input goes through the generator as overlapping img_size tiles
         (GeneratorModel.infer_tiled) and the three panels are written at the source size.  The metrics compare the full-resolution
         prediction with the full-resolution normalised target."""
-        S, c = int(self.config['img_size']), int(self.config['channels'])
-        V = self.config.get('tile_overlap')
-        V = S // 4 if V is None else int(V)
+        S, c, V = int(self.config['img_size']), int(self.config['channels']), tile_overlap_of(self.config)
         lut = tiling.normalize_lut(self.ctx)
         self.generator.fold()           # once: the weights stand still while predicting
         for k, f in enumerate(files):
@@ -252,15 +251,10 @@ def parse_opt(argv=None):
                              "with its gradient on the GPU; 'ssim' (the reference's input-against-target term) is refused")
     parser.add_argument('--input-img-orient', type=str, default='left', choices=['left', 'right'], help='whether input image is on left (i.e. target right) or vice-versa')
     parser.add_argument('--lambda', type=int, default=100, help='lambda value for secondary generator loss (L1 / dSSIM)')
-    parser.add_argument('--predict-resolution', type=str, default='resized', choices=['resized', 'native'],
-                        help="--predict only: 'resized' = every half resized to --img-size first (the reference); 'native' = predict "
-                             "at the source size from overlapping --img-size tiles blended on the GPU (needs --predict-training false)")
-    parser.add_argument('--tile-overlap', type=int, default=None,
-                        help='--predict-resolution native: pixels neighbouring tiles share, 0 ..= img-size / 2 (default img-size / 4)')
-    parser.add_argument('--quality-metrics', type=str, default='false', choices=['true', 'false'],
-                        help="image quality of the generator against the ground truth (SSIM as tf.image.ssim, PSNR, MAE), computed on "
-                             "the GPU: --train writes logs/val_quality.json (per epoch) and logs/test_quality.json, --predict "
-                             "writes logs/prediction_metrics.json")
+    add_prediction_flags(parser, image='half', resized=' (the reference)',
+                         metrics="image quality of the generator against the ground truth (SSIM as tf.image.ssim, PSNR, MAE), computed on "
+                                 "the GPU: --train writes logs/val_quality.json (per epoch) and logs/test_quality.json, --predict "
+                                 "writes logs/prediction_metrics.json")
     args = parser.parse_args(argv)
     if args.generator_loss == 'ssim':
         # pix2pix.py:182-184 computes tf.image.ssim(input_image, target): no gradient reaches the generator and the total becomes
@@ -270,13 +264,7 @@ def parse_opt(argv=None):
                      "carries no gradient, pix2pix.py:182-184); use the default --generator-loss l1, or --generator-loss dssim "
                      "for 1 - SSIM(generated, target)")
     check_common_flags(parser, args)
-    if args.tile_overlap is None:
-        args.tile_overlap = args.img_size // 4
-    if not 0 <= args.tile_overlap <= args.img_size // 2:
-        parser.error(f"--tile-overlap {args.tile_overlap} is outside [0, img-size / 2 = {args.img_size // 2}]")
-    if args.predict_resolution == 'native' and not (args.predict and args.predict_training == 'false'):
-        parser.error("--predict-resolution native requires --predict and --predict-training false: tiles are only meaningful in "
-                     "inference mode (batch statistics over the tiles of one image are not the reference's semantics)")
+    check_prediction_flags(parser, args)
     return args
 
 
@@ -284,11 +272,10 @@ def _write_quality_logs(p2p, run, test):
     """--quality-metrics true: the per-epoch validation metrics and those of the test set, also on the averaged weights."""
     if str(p2p.config.get('quality_metrics', 'false')) != 'true':
         return
-    finite = lambda per_epoch: {k: [v if np.isfinite(v) else None for v in vs] for k, vs in per_epoch.items()}
-    run.write_json('val_quality.json', finite(p2p.val_quality))
+    run.write_json('val_quality.json', finite_lists(p2p.val_quality))
     run.write_json('test_quality.json', summary(p2p.evaluate(test)))
     if p2p._ema_active():
-        run.write_json('val_quality_ema.json', finite(p2p.val_quality_ema))
+        run.write_json('val_quality_ema.json', finite_lists(p2p.val_quality_ema))
         with p2p.generator_ema.averaged():
             run.write_json('test_quality_ema.json', summary(p2p.evaluate(test)))
 

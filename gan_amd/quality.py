@@ -76,11 +76,12 @@ class QualityMeter:
             return None, 0
         return torch.cat(self.rows).double().sum(dim=0), len(self)
 
-    def drain(self):
-        """-> {'SSIM': [...], 'PSNR': [...], 'MAE': [...], 'MSE': [...]} per image in the order added; empties the meter."""
+    def drain(self, keys=KEYS):
+        """-> {'SSIM': [...], 'PSNR': [...], 'MAE': [...], 'MSE': [...]} per image in the order added; empties the meter.
+        keys: the names of the columns of the rows that were added (gan_amd.cycle_quality adds wider rows)."""
         rows, self.rows = self.rows, []
         host = torch.cat(rows).cpu().tolist() if rows else []
-        return {k: [r[j] for r in host] for j, k in enumerate(KEYS)}
+        return {k: [r[j] for r in host] for j, k in enumerate(keys)}
 
 
 def _finite(v):

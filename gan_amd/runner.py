@@ -137,6 +137,40 @@ def add_common_flags(parser, argv, generator: str, networks: str) -> None:
                         help='gradient exchange: one all-reduce per bucket, or fp32 reduce-scatter + all-gather in the wire format')
 
 
+def add_prediction_flags(parser, image: str, resized: str, metrics: str) -> None:
+    """--predict-resolution / --tile-overlap / --quality-metrics.  Each driver declares them with its own nouns: Pix2Pix among the
+    flags of vars(opt), CycleGAN in the slots of its option class.  image: what one input image is ('half' / 'image'); resized:
+    the parenthesis after 'resized first'; metrics: the help text of --quality-metrics."""
+    parser.add_argument('--predict-resolution', type=str, default='resized', choices=['resized', 'native'],
+                        help=f"--predict only: 'resized' = every {image} resized to --img-size first{resized}; 'native' = predict "
+                             "at the source size from overlapping --img-size tiles blended on the GPU (needs --predict-training false)")
+    parser.add_argument('--tile-overlap', type=int, default=None,
+                        help='--predict-resolution native: pixels neighbouring tiles share, 0 ..= img-size / 2 (default img-size / 4)')
+    parser.add_argument('--quality-metrics', type=str, default='false', choices=['true', 'false'], help=metrics)
+
+
+def check_prediction_flags(parser, args) -> None:
+    """After check_common_flags: the default and the range of --tile-overlap, and what --predict-resolution native needs."""
+    if args.tile_overlap is None:
+        args.tile_overlap = args.img_size // 4
+    if not 0 <= args.tile_overlap <= args.img_size // 2:
+        parser.error(f"--tile-overlap {args.tile_overlap} is outside [0, img-size / 2 = {args.img_size // 2}]")
+    if args.predict_resolution == 'native' and not (args.predict and args.predict_training == 'false'):
+        parser.error("--predict-resolution native requires --predict and --predict-training false: tiles are only meaningful in "
+                     "inference mode (batch statistics over the tiles of one image are not the reference's semantics)")
+
+
+def tile_overlap_of(config) -> int:
+    """config['tile_overlap'], or img_size / 4 for a config that was not built by a parser."""
+    V = config.get('tile_overlap')
+    return int(config['img_size']) // 4 if V is None else int(V)
+
+
+def finite_lists(per_epoch: dict) -> dict:
+    """{key: [epoch mean, ...]} ready for strict JSON: a non-finite value (the PSNR of an exact match) becomes null."""
+    return {k: [v if np.isfinite(v) else None for v in vs] for k, vs in per_epoch.items()}
+
+
 def check_common_flags(parser, args) -> None:
     if not 0.0 <= args.ema_decay < 1.0:
         parser.error(f"--ema-decay {args.ema_decay} is outside [0, 1)")
@@ -268,12 +302,13 @@ def drive(opt, model_class, name: str, *, strict_logs: bool, max_to_keep: int, c
             if info.is_main:
                 dataset = model.image_pipeline(predict=True)[0]
                 checkpoint.restore(latest_checkpoint(opt.weights))
-                weights = contextlib.nullcontext()
+                weights = contextlib.ExitStack()
                 if opt.predict_weights == 'ema':
-                    if not model.averages[0].loaded:
+                    if not all(avg.loaded for avg in model.averages):
                         raise SystemExit(f"--predict-weights ema: checkpoint holds no averaged weights ({opt.weights}); "
                                          "train with --ema-decay")
-                    weights = model.averages[0].averaged()
+                    for avg in model.averages:      # every averaged generator: CycleGAN's cycle runs on the pair that was averaged together
+                        weights.enter_context(avg.averaged())
                 with weights:
                     metrics = model.predict(dataset, run.root)
                 if metrics is not None:

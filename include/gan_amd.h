@@ -655,6 +655,31 @@ typedef struct GanTileGatherDesc {
  * GAN_E_SHAPE: as gan_tile_grid.  All found before anything is launched; enqueue-only. */
 int gan_tile_gather_u8(const GanTileGatherDesc* d, gan_stream_t stream);
 
+/* The same cut from a float image (no table): tiles [t0, t0 + n) of an fp32 / bf16 / fp16 image [h][src_pitch / c][c], for instance
+ * the blended fp32 prediction of one generator as the input of the next (the cycle of a CycleGAN at the source resolution):
+ *     dst[t - t0][r][x][ch] = dst_dtype( src[(oy(t) + r) * src_pitch + (col0 + ox(t) + x) * c + ch] )
+ * Geometry and tile numbering are gan_tile_grid's.  src_dtype == dst_dtype copies the bits; an fp32 source is rounded to nearest
+ * into a 16-bit destination, as every conversion here; no other pair is taken.  Only the c real channels of a destination pixel
+ * are written; every source index is clamped to [0, src_elems). */
+typedef struct GanTileGatherFDesc {
+  uint32_t struct_size;
+  int32_t src_dtype;           /* storage of src: GAN_F32 | GAN_BF16 | GAN_F16 */
+  const void* src;             /* device: first element of the image's first row; c interleaved channels; element-aligned */
+  int64_t src_elems;           /* elements readable from src */
+  int32_t src_pitch;           /* elements between consecutive source rows */
+  int32_t col0;                /* first source column (pixels) of the part used */
+  int32_t h, w;                /* size of the part used */
+  int32_t c;                   /* 1 or 3 */
+  int32_t tile, overlap;
+  int32_t t0, n;               /* tiles of this launch */
+  int32_t dst_dtype;           /* storage of dst: src_dtype, or any of the three for an fp32 source */
+  GanTensor dst;               /* n x tile x tile, c channels, own pitch; ptr aligned to its element size */
+} GanTileGatherFDesc;
+/* GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype or dtype pair, c not 1 or 3, dst not n x tile x tile x c, pitch < c,
+ * t0 / n outside the grid, src / dst.ptr not element-aligned, col0 / src_pitch / the last row outside src_elems.
+ * GAN_E_SHAPE: as gan_tile_grid.  All found before anything is launched; enqueue-only, capturable. */
+int gan_tile_gather(const GanTileGatherFDesc* d, gan_stream_t stream);
+
 /* Tiles [t0, t0 + n) of a typed network output, added into the dense fp32 image [h][w][c] with the weights above.  One thread
  * owns an output pixel: it finds the tiles of this launch that cover it, adds them in ascending tile order and writes once -
  * no atomics, bit-identical from call to call.  A pixel that no tile of the launch covers keeps its value (accumulate = 1) or
