@@ -148,6 +148,16 @@ class GanPoolDesc(_Desc):
                 ("capacity", C.c_int32), ("stream_id", C.c_uint32), ("seed", C.c_uint64), ("state", C.c_void_p)]
 
 
+class GanDiffAugParams(C.Structure):
+    _fields_ = [("tx", C.c_int32), ("ty", C.c_int32), ("cut_x0", C.c_int32), ("cut_y0", C.c_int32), ("cut_w", C.c_int32),
+                ("cut_h", C.c_int32), ("brightness", C.c_float), ("saturation", C.c_float)]
+
+
+class GanDiffAugDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("src", GanTensor), ("dst", GanTensor), ("group_c", C.c_int32),
+                ("sample0", C.c_int32), ("params", C.c_void_p), ("direction", C.c_int32)]
+
+
 class GanLrSchedule(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("lr", C.c_float), ("end_factor", C.c_float), ("decay_start", C.c_int32),
                 ("decay_end", C.c_int32)]
@@ -215,6 +225,10 @@ SYMBOLS = {
     "gan_unpack": (C.c_int, [C.c_int32, C.POINTER(GanTensor), C.c_void_p, C.c_void_p]),
     "gan_copy_view": (C.c_int, [C.c_int32, C.POINTER(GanTensor), C.POINTER(GanTensor), C.c_void_p]),
     "gan_pool_exchange": (C.c_int, [C.POINTER(GanPoolDesc), C.c_void_p]),
+    "gan_diffaug_policy": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint32)]),
+    "gan_diffaug_draw": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
+                                   C.c_void_p]),
+    "gan_diffaug_apply": (C.c_int, [C.POINTER(GanDiffAugDesc), C.c_void_p]),
     "gan_bias_grad": (C.c_int, [C.c_int32, C.POINTER(GanTensor), C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "gan_grad_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gan_grad_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),

@@ -185,7 +185,7 @@ class AdamConfig:
 def _step_state(ctx, st):
     """Device state a warm-up pass of capture() advances besides weights and Adam moments: the fp16 loss-scale state and the
     per-call dropout draw counters (every new batch size captures a new step: without this each capture would move them), and
-    the image pools of a CycleGAN step, state and contents."""
+    the image pools of a CycleGAN step, state and contents, and the draw counter of a differentiable augmentation."""
     ts = [ctx.ls] if ctx.ls is not None else []
     ts += [net.params.lr_now for net in st.nets() if net.params.lr_now is not None]       # (the rate a scheduled update reports)
     for call in vars(st).values():
@@ -194,6 +194,8 @@ def _step_state(ctx, st):
             ts.append(md)
     for pool in getattr(st, 'pools', None) or ():
         ts += pool.tensors()
+    if getattr(st, 'diffaug', None) is not None:          # (the draw counter and the table of a Pix2Pix step with --diffaugment)
+        ts += st.diffaug.tensors()
     return [(t, t.clone()) for t in ts]
 
 

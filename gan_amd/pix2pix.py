@@ -14,6 +14,7 @@ from . import data as D
 from . import ddp
 from . import tiling
 from .base_gan import GAN
+from .diffaug import DiffAugment, parse_policies
 from .quality import QualityMeter, image_quality, summary
 from .steps import Pix2PixStep
 from .runner import (add_common_flags, add_prediction_flags, check_common_flags, check_prediction_flags, drive, finite_lists,
@@ -49,6 +50,7 @@ class Pix2Pix(GAN):
         self.generator_optimizer = mk().bind(self.generator.net.params)
         self.discriminator_optimizer = mk().bind(self.discriminator.net.params)
         (self.generator_ema,) = self._init_trainer(averaged=(self.generator,))
+        self.diffaug = None        # --diffaugment: one DiffAugment for the training steps of every batch size (built with the first of them)
 
     def networks(self):
         return (self.generator, self.discriminator)
@@ -105,12 +107,22 @@ class Pix2Pix(GAN):
         gan_loss2 = _dssim_eager(gen_output, target) if kind == 'dssim' else (target - gen_output).abs().mean()
         return gan_loss + (self.config['lambda'] * gan_loss2), gan_loss, gan_loss2
 
+    def _diffaug_for(self, training):
+        """config['diffaugment']: the augmentation of what the discriminator sees in training steps; the
+        model owns the table and the draw counter, as it owns a pool - a last partial batch continues the same sequence."""
+        policies = parse_policies(self.config.get('diffaugment') or '')
+        if not training or not policies:
+            return None
+        if self.diffaug is None:
+            self.diffaug = DiffAugment(self.ctx, policies, seed=int(self.config.get('seed', 123)))
+        return self.diffaug
+
     def _build_step(self, batch, training):
         return Pix2PixStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
                            lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
                            seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net),
                            generator_loss=self.config.get('generator_loss', 'l1'), gan_loss=self.config.get('gan_loss', 'bce'),
-                           lr_schedule=self.lr_schedule if training else None)
+                           lr_schedule=self.lr_schedule if training else None, diffaug=self._diffaug_for(training))
 
     def train_step(self, input_image, target, training: bool = True):
         """-> (gen_total_loss, gen_gan_loss, gen_gan_loss2, disc_loss) as 0-d device tensors (no host sync)."""
@@ -240,6 +252,13 @@ class Pix2Pix(GAN):
                                                                  ('Predicted Image', pred.cpu().numpy())], gray=self.config['channels'] == '1')
 
 
+class Options(argparse.Namespace):
+    """The parsed Pix2Pix command line.  --diffaugment is this driver's own training option: it lives in a slot beside the flag
+    dictionary (vars(opt) stays the set of flags the two drivers are compared on) and reaches the model's config - and
+    config.json - through runner.config_of."""
+    __slots__ = ('diffaugment',)
+
+
 def parse_opt(argv=None):
     """Same flags / defaults / assertions as pix2pix.py:341-377 (+ this project's: runner.add_common_flags and the ones below)."""
     argv = sys.argv[1:] if argv is None else argv
@@ -249,13 +268,17 @@ def parse_opt(argv=None):
     parser.add_argument('--generator-loss', type=str, default='l1', choices=['l1', 'ssim', 'dssim'],
                         help="secondary generator loss: 'l1' = mean |target - generated|; 'dssim' = 1 - mean SSIM(generated, target), computed "
                              "with its gradient on the GPU; 'ssim' (the reference's input-against-target term) is refused")
+    parser.add_argument('--diffaugment', type=str, default='',
+                        help="differentiable augmentation of everything the discriminator sees in training steps (Zhao et al. 2020), "
+                             "for small datasets: a comma-separated subset of translation,cutout,brightness,saturation; default: none "
+                             "(the reference)")
     parser.add_argument('--input-img-orient', type=str, default='left', choices=['left', 'right'], help='whether input image is on left (i.e. target right) or vice-versa')
     parser.add_argument('--lambda', type=int, default=100, help='lambda value for secondary generator loss (L1 / dSSIM)')
     add_prediction_flags(parser, image='half', resized=' (the reference)',
                          metrics="image quality of the generator against the ground truth (SSIM as tf.image.ssim, PSNR, MAE), computed on "
                                  "the GPU: --train writes logs/val_quality.json (per epoch) and logs/test_quality.json, --predict "
                                  "writes logs/prediction_metrics.json")
-    args = parser.parse_args(argv)
+    args = parser.parse_args(argv, namespace=Options())
     if args.generator_loss == 'ssim':
         # pix2pix.py:182-184 computes tf.image.ssim(input_image, target): no gradient reaches the generator and the total becomes
         # a (batch,) vector.  That degenerate term is not built here, and training silently with L1
@@ -263,6 +286,10 @@ def parse_opt(argv=None):
         parser.error("--generator-loss ssim is not supported by gan_amd (the reference's SSIM term compares input with target and "
                      "carries no gradient, pix2pix.py:182-184); use the default --generator-loss l1, or --generator-loss dssim "
                      "for 1 - SSIM(generated, target)")
+    try:
+        args.diffaugment = ','.join(parse_policies(args.diffaugment))        # (canonical order: what config.json records)
+    except ValueError as e:
+        parser.error(f"--diffaugment: {e}")
     check_common_flags(parser, args)
     check_prediction_flags(parser, args)
     return args

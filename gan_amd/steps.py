@@ -17,7 +17,8 @@ from typing import NamedTuple
 import torch
 
 from . import _lib as L
-from .nets import Ctx, DiscriminatorNet, GeneratorNet, LrSchedule
+from .diffaug import MAX_RECORDS
+from .nets import Buf, Ctx, DiscriminatorNet, GeneratorNet, LrSchedule
 
 
 # Other threads of the process may call into the runtime while a step is being captured (the RCCL watchdog of
@@ -308,7 +309,8 @@ class Pix2PixStep(_StepBase):
     ddp_wire_direct = True       # bf16 all-reduce exchange: wgrad launches write their gradients straight into the wire buffer
 
     def __init__(self, ctx: Ctx, batch, size, channels=1, lam=100.0, lr=2e-4, beta_1=0.5, beta_2=0.999,
-                 seed=123, dropout=True, nets=None, mask_stream=0, generator_loss='l1', gan_loss='bce', lr_schedule=None):
+                 seed=123, dropout=True, nets=None, mask_stream=0, generator_loss='l1', gan_loss='bce', lr_schedule=None,
+                 diffaug=None):
         if generator_loss not in ('l1', 'dssim'):
             raise ValueError(f"generator_loss {generator_loss!r}: 'l1' or 'dssim'")
         super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=8, gan_loss=gan_loss)
@@ -327,6 +329,15 @@ class Pix2PixStep(_StepBase):
                                  wgrads_on_side_lane=ctx.lanes)
         self.d = self.D.new_call(batch, size, calls=2)
         self._set_lr_schedule(lr_schedule)
+        # differentiable augmentation of what D sees (gan_amd/diffaug.py): a training pass stages the raw
+        # [input | target] images here, D's input buffer receives their augmented images, and D's input gradient arrives in
+        # aug_dgen (D's own, otherwise unused, input-gradient buffer) on its way to the generator
+        self.diffaug = diffaug
+        if diffaug is not None:
+            if 2 * batch > MAX_RECORDS:
+                raise ValueError(f"diffaug: batch {batch} needs {2 * batch} records, at most {MAX_RECORDS}")
+            self.aug_raw = Buf(ctx, 2 * batch, size, size, 8)
+            self.aug_dgen = self.d.dxin
 
     def nets(self):
         return (self.G, self.D)
@@ -361,23 +372,39 @@ class Pix2PixStep(_StepBase):
             d.backward_params()
             return self.losses
         # inputs -> typed, channel-padded buffers.  D input = concat([inp, tar|gen]) (base_gan.py:139)
-        self._pack_multi([(inp, g.xin.view(0, Cc)), (inp, d.xin.view(0, Cc, 0, B)), (inp, d.xin.view(0, Cc, B, B)),
-                          (tar, d.xin.view(Cc, Cc, 0, B))])
+        aug = self.diffaug if training else None         # (validation: nothing is augmented, the launches of a step without it)
+        xin = self.aug_raw if aug is not None else d.xin
+        self._pack_multi([(inp, g.xin.view(0, Cc)), (inp, xin.view(0, Cc, 0, B)), (inp, xin.view(0, Cc, B, B)),
+                          (tar, xin.view(Cc, Cc, 0, B))])
+        if aug is not None:                               # records 0..B-1: the real samples, B..2B-1: the generated ones
+            aug.draw(2 * B, self.S, self.S)
         # (the optimiser-carrying wgrad launches of G's backward need this step's lr_t: nothing before them reads it)
         dreal = bool(self.ctx.lanes and self.dreal_on_side_lane)
         adam_begun = bool(dreal and self.adam_begin_early and phase == Phase.FULL and mode.fuse_adam)
-        self._forward_and_losses(dreal, adam_begun)
+        self._forward_and_losses(dreal, adam_begun, aug)
         if training:
-            d.backward_input(1, dst=g.dgen2.view(0, Cc), c0=Cc)        # dL_G/d gen through D(fake), pre-update D: the `gen` channels only
+            if aug is not None:                           # ... of the augmented image, carried back through the transform's transpose
+                d.backward_input(1, dst=self.aug_dgen.view(0, Cc), c0=Cc)
+                aug.apply(self.aug_dgen.view(0, Cc), g.dgen2.view(0, Cc), Cc, B, backward=True)
+            else:
+                d.backward_input(1, dst=g.dgen2.view(0, Cc), c0=Cc)    # dL_G/d gen through D(fake), pre-update D: the `gen` channels only
             if phase != Phase.HEAD:                                   # (HEAD: the caller stages G's backward)
                 self._backward(phase, mode, adam_begun)
         return self.losses                                            # Adam: _update() (pix2pix.py:213-216)
 
-    def _forward_and_losses(self, dreal, begin_adam):
-        """G, D(real), D(fake) and the four losses with their gradients.  begin_adam: G's gan_adam_begin heads D(real)'s lane."""
+    def _forward_and_losses(self, dreal, begin_adam, aug=None):
+        """G, D(real), D(fake) and the four losses with their gradients.  begin_adam: G's gan_adam_begin heads D(real)'s lane.
+        aug: the DiffAugment whose table this step has drawn - D's input is the augmented image of the staged raw one (aug_raw)."""
         B, Cc, g, d, ctx = self.B, self.C, self.g, self.d, self.ctx
         main = ctx.lane_stream(0)
         side = ctx.lane_stream(2) if ctx.lanes else None
+        raw = self.aug_raw if aug is not None else d.xin             # where the un-augmented [input | target] images are
+
+        def augment_inputs(stream=None, real=True, fake=True):
+            if aug is not None and real:      # [input | target] of the real samples: two images per sample, one record
+                aug.apply(raw.view(0, 2 * Cc, 0, B), d.xin.view(0, 2 * Cc, 0, B), Cc, 0, stream=stream)
+            if aug is not None and fake:      # the input channels of the generated samples (their records also serve the generated channels)
+                aug.apply(raw.view(0, Cc, B, B), d.xin.view(0, Cc, B, B), Cc, B, stream=stream)
         if dreal:
             # D(real) does not depend on the generator: it starts on lane 2 when G reaches its inner layers (down3 on:
             # launch-bound layers that leave the chip idle; measured best start point, +0.8 %) and D(fake) follows G on the main chain.  Same
@@ -385,10 +412,14 @@ class Pix2PixStep(_StepBase):
             def start_dreal():
                 side.wait_stream(main)
                 pre = self.G.params.adam_begin_ops(self.lr, self.b1, self.b2) if begin_adam else []
-                ctx.run_on(pre + d.forward_part_ops(0, lane=2), side)
+                ctx.run_on(pre, side)
+                augment_inputs(side, fake=False)
+                ctx.run_on(d.forward_part_ops(0, lane=2), side)
+                augment_inputs(side, real=False)                      # (off the main chain; joined below, before D(fake))
             g.forward(inner_hook=start_dreal)                         # pix2pix.py:200
             ctx.join(main, side)                                      # D(real) done (its BatchNorm updates come first)
         else:
+            augment_inputs()
             g.forward()                                               # pix2pix.py:200
         # generator loss (pix2pix.py:167-188): BCE(1, D(fake)) + lambda * mean|target - gen| (or, generator_loss 'dssim', lambda *
         # (1 - mean SSIM(gen, target)): same operands, stream and outputs); discriminator loss
@@ -397,8 +428,11 @@ class Pix2PixStep(_StepBase):
         if side is not None:
             side.wait_stream(main)
         secondary = self._dssim if self.generator_loss == 'dssim' else self._l1
-        secondary(g.out_view(), d.xin.view(Cc, Cc, 0, B), 2, 1.0, False, self.lam, g.dgen.view(0, Cc), stream=side)
-        self._copy(g.out_view(), d.xin.view(Cc, Cc, B, B))
+        secondary(g.out_view(), raw.view(Cc, Cc, 0, B), 2, 1.0, False, self.lam, g.dgen.view(0, Cc), stream=side)
+        if aug is not None:
+            aug.apply(g.out_view(), d.xin.view(Cc, Cc, B, B), Cc, B)
+        else:
+            self._copy(g.out_view(), d.xin.view(Cc, Cc, B, B))
         if dreal:
             ctx.run(d.forward_part_ops(1))                            # pix2pix.py:203
         else:

@@ -491,6 +491,71 @@ typedef struct GanPoolDesc {
  * GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype, capacity < 1, n / h / w / c of src and dst differ or are < 1, pitch < c,
  * a pointer not aligned to its element size.  GAN_E_SHAPE: h * w * pitch of an image >= 2^31.  All found before the launch. */
 int gan_pool_exchange(const GanPoolDesc* d, gan_stream_t stream);
+/* Differentiable augmentation of what a discriminator sees (no counterpart in the reference; Zhao et al., "Differentiable
+ * Augmentation for Data-Efficient GAN Training", NeurIPS 2020): colour (brightness, saturation), then
+ * translation with zero fill, then cutout, per image, the same family on real and generated inputs, and the exact transpose of
+ * that map for the generator's gradient.  One record per image of a discriminator invocation, in device memory: */
+typedef struct GanDiffAugParams {   /* 32 bytes */
+  int32_t tx, ty;                   /* translation in pixels (tx along w, ty along h): y(p) reads x(p - t) */
+  int32_t cut_x0, cut_y0, cut_w, cut_h;  /* cut rectangle in OUTPUT coordinates, already clipped to the image; cut_w = 0: none */
+  float brightness;                 /* added to every real channel */
+  float saturation;                 /* s: x_c -> (x_c - m) * s + m, m = mean over the channels of the pixel's own image */
+} GanDiffAugParams;
+enum { GAN_DIFFAUG_TRANSLATION = 1, GAN_DIFFAUG_CUTOUT = 2, GAN_DIFFAUG_BRIGHTNESS = 4, GAN_DIFFAUG_SATURATION = 8 };
+/* Host only: "translation,cutout" (any comma-separated subset of translation, cutout, brightness, saturation; "" = none) -> the
+ * policy bit mask.  GAN_E_ARG: NULL names / policy, an unknown or empty name. */
+int gan_diffaug_policy(const char* names, uint32_t* policy);
+/* params[0 .. n-1] <- fresh draws for images of h x w pixels, then *launches += 1.  One launch of one workgroup; enqueue-only and
+ * capturable: `launches` (device int32, zero-initialised by the caller) is the draws' own counter - not an Adam step counter -
+ * every thread reads it before the one store that advances it, so a replayed graph draws anew.  Bit layout of the draws
+ * (mix64 = the dropout masks' counter hash; lo(h) = h & 0xffffffff, hi(h) = h >> 32, both as uint64):
+ *     key = mix64(seed ^ ((uint64)(uint32)launches << 32) ^ stream_id),   h_k = mix64(key ^ (uint64)(4 * i + k)) for record i
+ *     translation: Tx = (w + 4) / 8, Ty = (h + 4) / 8 (integer division: round(size / 8));
+ *                  tx = (int)((lo(h_0) * (2 Tx + 1)) >> 32) - Tx,   ty = (int)((hi(h_0) * (2 Ty + 1)) >> 32) - Ty
+ *     cutout:      per axis (x: size = w, 32 bits = lo(h_1); y: size = h, 32 bits = hi(h_1)):  cs = size / 2,
+ *                  N = size + (1 - cs % 2),  off = (bits * N) >> 32  (uniform on 0 .. N-1, the centre offset of the paper's code),
+ *                  start = off - cs / 2;  the rectangle [start, start + cs) intersected with [0, size): cut_x0 / cut_w, cut_y0 / cut_h
+ *                  (never empty for size >= 2; size = 1: cs = 0, nothing is cut, cut_w = cut_h = 0)
+ *     brightness:  (float)(h_2 >> 40) * 2^-24 - 0.5     in [-0.5, 0.5), exact in fp32
+ *     saturation:  (float)(h_3 >> 40) * 2^-23           in [0, 2), exact in fp32
+ * A policy whose bit is not set in `policy` writes its neutral value: tx = ty = 0; cut_x0 = cut_y0 = cut_w = cut_h = 0;
+ * brightness = 0; saturation = 1.
+ * GAN_E_ARG and no launch: NULL params / launches, n < 1 or n > 128, h or w < 1, policy bits beyond the four, params not 4-byte
+ * aligned, launches not 4-byte aligned. */
+int gan_diffaug_draw(GanDiffAugParams* params, int32_t n, int32_t h, int32_t w, uint32_t policy, uint64_t seed,
+                     uint32_t stream_id, int32_t* launches, gan_stream_t stream);
+/* One direction of the map for the images of a view.  With P = params[sample0 + b] for image b, p a pixel, ch a channel:
+ *   forward  (direction 0):  y(p, ch) = cut(p) ? 0 : (p - t inside the image ? colour(x(p - t, ch)) : 0)
+ *                            colour(x_ch) = (x_ch - m) * s + m + brightness,   m = mean of the group's channels at that pixel
+ *                            (group_c = 1: m = x_ch and s drops out: x_ch + brightness)
+ *   backward (direction 1):  dx(q, ch) = (q + t inside the image and not cut(q + t)) ? s * dy(q + t, ch) + (1 - s) * mean_group(dy(q + t, .)) : 0
+ *                            (src = dy, dst = dx; group_c = 1: dy(q + t, ch))
+ * cut(p) = cut_w > 0 and cut_x0 <= p.x < cut_x0 + cut_w and cut_y0 <= p.y < cut_y0 + cut_h.  The backward direction is the exact
+ * transpose of the forward one and a gather as well: no atomics, the same inputs give the same bits.  Arithmetic in fp32
+ * (m = (x_0 + x_1 + x_2) / 3, one fused multiply-add, one add), rounded once to the storage dtype; where colour is the identity
+ * (forward: brightness = 0 and, for group_c = 3, s = 1; backward: s = 1 or group_c = 1) bits are moved and nothing is computed;
+ * the fill is +0.  Only the c real channels of dst are written: pad channels of a wider pitch and memory outside the view keep
+ * their bits; pad channels of src are never used (they may hold NaN).  src and dst must not overlap.  One launch, enqueue-only and
+ * capturable, no workspace. */
+typedef struct GanDiffAugDesc {
+  uint32_t struct_size;
+  int32_t dtype;               /* GAN_F32 | GAN_BF16 | GAN_F16: storage of src and dst */
+  GanTensor src;               /* n images of h x w, c channels, own pitch: only read */
+  GanTensor dst;               /* out: same n, h, w, c, own pitch */
+  int32_t group_c;             /* 1 or 3: channels of one image; c is a multiple of it ([input | target] with c = 2 * group_c is two
+                                  images per sample: saturation is taken inside each group) */
+  int32_t sample0;             /* image b of the view uses params[sample0 + b]; >= 0 */
+  const GanDiffAugParams* params;   /* device: at least sample0 + n records; only read */
+  int32_t direction;           /* 0 forward, 1 backward (transpose) */
+} GanDiffAugDesc;
+/* A thread owns a pixel.  Where a pixel of src is one aligned 16-byte unit (pitch * element size = 16, 16-byte aligned src.ptr,
+ * c within it: the step's bf16 / fp16 buffers of pitch 8, fp32 of pitch 4) it is fetched with one 16-byte load; element loads
+ * placed by (pixel, channel) otherwise.  dst is always written by elements, channel by channel: launches that fill other channels
+ * of the same pixels (the generated channels beside the input channels of a discriminator input) may run beside this one.
+ * GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype, n / h / w / c of src and dst differ or are < 1, pitch < c, group_c not 1
+ * or 3, c not a multiple of group_c, sample0 < 0, direction not 0 or 1, a tensor pointer not aligned to its element size, params
+ * not 4-byte aligned.  GAN_E_SHAPE: h * w * pitch of an image >= 2^31, n > 65535.  All found before the launch. */
+int gan_diffaug_apply(const GanDiffAugDesc* d, gan_stream_t stream);
 /* bias gradient: dbias[c] (+)= sum over n,h,w of dy[...,c]; dy.c 8-padded, dbias has dy.c entries.
  * workspace >= gan_norm_workspace_bytes(1, dy.c, n*h*w). */
 int gan_bias_grad(int32_t dtype, const GanTensor* dy, float* dbias, int32_t accumulate, void* workspace,
