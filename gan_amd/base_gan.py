@@ -25,7 +25,9 @@ from . import tiling
 from .checkpoint import DISC_LAYERS, GEN_LAYERS, tf_variable_key
 from .ema import WeightAverage
 from .nets import Ctx, DiscriminatorNet, GeneratorNet, workspace_mb_for
+from .pool import STREAM_X, STREAM_Y
 from .runner import lr_schedule_for, run_epochs
+from .train_state import TrainState
 
 
 def _to_dev(x, ctx):
@@ -67,6 +69,7 @@ class GeneratorModel(_Model):
 
     def __init__(self, net: GeneratorNet, obj_name='generator'):
         self.net, self.obj_name, self._calls, self._eval_calls = net, obj_name, {}, {}
+        self._restored_draws = {}      # (batch, size) -> dropout draw counters of a restored train_state, for calls not built yet
 
     def __call__(self, x, training=True):
         if not training:
@@ -77,6 +80,8 @@ class GeneratorModel(_Model):
         key = (B, S)
         if key not in self._calls:
             self._calls[key] = self.net.new_call(B, S, dropout=True, stream_id=40)     # (ids 0..5 / 16..21: the train / validation steps' generator calls)
+            if key in self._restored_draws:
+                self._calls[key].mask_draws.copy_(torch.from_numpy(self._restored_draws.pop(key).astype(np.int32)))
         call = self._calls[key]
         call.set_input(x)
         call.forward()
@@ -182,21 +187,46 @@ class AdamConfig:
                     ps.tensor(name, slot).copy_(torch.from_numpy(sd[k].astype(np.float32)).view(ps.entries[name][1]))
 
 
-def _step_state(ctx, st):
-    """Device state a warm-up pass of capture() advances besides weights and Adam moments: the fp16 loss-scale state and the
-    per-call dropout draw counters (every new batch size captures a new step: without this each capture would move them), and
-    the image pools of a CycleGAN step, state and contents, and the draw counter of a differentiable augmentation."""
-    ts = [ctx.ls] if ctx.ls is not None else []
-    ts += [net.params.lr_now for net in st.nets() if net.params.lr_now is not None]       # (the rate a scheduled update reports)
-    for call in vars(st).values():
+def pool_state(pool):
+    """name -> tensor of one image pool (pool_y serves D_y, pool_x D_x)."""
+    name = {STREAM_Y: 'pool_y', STREAM_X: 'pool_x'}.get(pool.stream_id, f'pool_{pool.stream_id}')
+    return {f'{name}/{part}': t for part, t in zip(('state', 'storage'), pool.tensors())}
+
+
+def diffaug_state(aug):
+    return {f'diffaug/{part}': t for part, t in zip(('counter', 'table'), aug.tensors())}
+
+
+def named_step_state(ctx, st, prefix='', net_names=None):
+    """Device state a warm-up pass of capture() advances besides weights and Adam moments, name -> tensor in a fixed order: the
+    fp16 loss-scale state and the per-call dropout draw counters (every new batch size captures a new step: without this each
+    capture would move them), and the image pools of a CycleGAN step, state and contents, and the draw counter of a differentiable
+    augmentation.  What belongs to the step object alone (the dropout counters of its calls) is named `<prefix><attribute>.mask_draws`;
+    what the step shares with the model's other steps - `ls`, `lr_now/<network>`, `pool_y/...`, `diffaug/...` - carries no prefix.
+    net_names: {id(network): name}; by default the position in st.nets().  This is also the device part of a checkpoint's
+    train_state (gan_amd/train_state.py)."""
+    out = {}
+    if ctx.ls is not None:
+        out['ls'] = ctx.ls
+    for i, net in enumerate(st.nets()):
+        if net.params.lr_now is not None:                 # (the rate a scheduled update reports)
+            out[f"lr_now/{(net_names or {}).get(id(net), i)}"] = net.params.lr_now
+    seen = set()
+    for attr, call in vars(st).items():
         md = getattr(call, 'mask_draws', None)
-        if isinstance(md, torch.Tensor):
-            ts.append(md)
+        if isinstance(md, torch.Tensor) and md.data_ptr() not in seen:
+            seen.add(md.data_ptr())
+            out[f'{prefix}{attr}.mask_draws'] = md
     for pool in getattr(st, 'pools', None) or ():
-        ts += pool.tensors()
+        out.update(pool_state(pool))
     if getattr(st, 'diffaug', None) is not None:          # (the draw counter and the table of a Pix2Pix step with --diffaugment)
-        ts += st.diffaug.tensors()
-    return [(t, t.clone()) for t in ts]
+        out.update(diffaug_state(st.diffaug))
+    return out
+
+
+def _step_state(ctx, st):
+    """named_step_state with a copy of every tensor, for _restore_step_state."""
+    return [(t, t.clone()) for t in named_step_state(ctx, st).values()]
 
 
 def _restore_step_state(saved):
@@ -278,6 +308,7 @@ class GAN(ABC):
         if ema_decay > 0 or str(self.config.get('predict_weights', 'raw')) == 'ema':
             warmup = str(self.config.get('ema_warmup', 'true')) == 'true'
             self.averages = tuple(WeightAverage(g, ema_decay, warmup) for g in averaged)
+        self.train_state = TrainState(self)      # the checkpoint object `train_state`: what --resume continues from
         return self.averages or (None,) * len(averaged)
 
     def _ema_active(self):
@@ -306,6 +337,7 @@ class GAN(ABC):
             self._restore(saved)
             _restore_step_state(extra)
             self._steps[key] = (st, replay)
+            self.train_state.apply_pending()       # restored state of this step object: behind the undo of the warm-up, not before
         return self._steps[key]
 
     def _snapshot(self):
@@ -331,9 +363,12 @@ class GAN(ABC):
             return f"learning rate: {lr:.3e}" + (f"\n{line}" if line else "")
         return lr_line
 
-    def _fit(self, output_path, checkpoint_manager, keys, train_batches, val_batches, steps_per_epoch, headline, sampler, after_epoch=None):
+    def _fit(self, output_path, checkpoint_manager, keys, train_batches, val_batches, steps_per_epoch, headline, sampler, after_epoch=None,
+             datasets=()):
         """The tail of fit(): train_batches() / val_batches() yield the arguments of train_step, steps_per_epoch updates per epoch;
-        sampler(path) draws the sample image of an epoch.  Rank 0 alone writes checkpoints and sample images."""
+        sampler(path) draws the sample image of an epoch.  Rank 0 alone writes checkpoints and sample images.  datasets: fit()'s
+        dataset arguments, whose pass counters belong to the train_state.  A model that restored a checkpoint with a train_state
+        continues behind that checkpoint's epoch; any other starts at epoch 1."""
         samples = os.path.join(output_path, 'test_images')
         if self.dist.is_main:
             os.makedirs(samples, exist_ok=True)
@@ -342,11 +377,19 @@ class GAN(ABC):
         if not self.dist.is_main:
             save = sample = (lambda *a: None)
         self.lr_schedule = lr_schedule_for(self.config, steps_per_epoch)      # (before the first training step is built and captured)
-        self.learning_rates = []
+        ts = self.train_state
+        resumed = ts.begin_fit(list(keys), steps_per_epoch, datasets, (self.val_quality, self.val_quality_ema))
+        lr_line = self._with_lr_line(after_epoch)
+
+        def epoch_done(epoch):      # the histories hold this epoch by now: a checkpoint written next says so
+            line = lr_line(epoch) if lr_line is not None else None
+            ts.epoch = epoch
+            return line
         return run_epochs(self.config['epochs'], list(keys), train_batches, val_batches, self.train_step, save, sample, headline,
                           epoch_mean=lambda acc, n: ddp.mean_over_ranks(acc, n, self.dist),
                           after_pass=(self.ctx.assert_no_stack_timeout if self.ctx.use_stacks else None),
-                          after_epoch=self._with_lr_line(after_epoch))
+                          after_epoch=epoch_done, checkpoint_every=int(self.config.get('checkpoint_every') or 5),
+                          hist=ts.hist, resumed_after=resumed[0] if resumed else 0)
 
     @abstractmethod
     def networks(self):

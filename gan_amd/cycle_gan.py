@@ -20,7 +20,7 @@ from .base_gan import GAN
 from .pool import STREAM_X, STREAM_Y, ImagePool
 from .quality import QualityMeter, summary
 from .steps import CycleGANStep
-from .runner import (add_common_flags, add_prediction_flags, check_common_flags, check_prediction_flags, drive, finite_lists,
+from .runner import (RESUME_SLOTS, add_common_flags, add_prediction_flags, check_common_flags, check_prediction_flags, drive, finite_lists,
                      save_panels, tile_overlap_of)
 from .utils import cyclegan_losses
 
@@ -209,7 +209,8 @@ class CycleGAN(GAN):
         return self._fit(output_path, checkpoint_manager, cyclegan_losses(), lambda: self._zipped(train_X, train_Y),
                          lambda: self._zipped(val_X, val_Y), min(len(train_X), len(train_Y)),
                          ('Total X->Y Generator Loss', 'Discriminator Y Loss'),
-                         lambda path: self.generate_images(self.generator_g, example[:1], path), after_epoch)
+                         lambda path: self.generate_images(self.generator_g, example[:1], path), after_epoch,
+                         datasets=(train_X, train_Y, val_X, val_Y, test))
 
     def predict(self, predict_ds, output_path: str):
         """As Pix2Pix.predict: config['predict_training'] 'false' runs generator_g in inference mode (InstanceNorm has no
@@ -273,7 +274,7 @@ class Options(argparse.Namespace):
     --predict-resolution, --tile-overlap) are this driver's own options: they live in slots beside the flag dictionary (vars(opt)
     stays the set of flags the two drivers have in common plus their input paths) and reach the model's config through
     runner.config_of."""
-    __slots__ = ('pool_size', 'quality_metrics', 'predict_resolution', 'tile_overlap')
+    __slots__ = ('pool_size', 'quality_metrics', 'predict_resolution', 'tile_overlap') + RESUME_SLOTS
 
 
 def parse_opt(argv=None):
@@ -286,8 +287,8 @@ def parse_opt(argv=None):
     parser.add_argument('--lambda', type=int, default=10, help='lambda parameter value')
     parser.add_argument('--pool-size', type=int, default=0,
                         help='image history pool per discriminator: it is trained on a random mix of current and earlier generated '
-                             'images (Zhu et al. 2017 use 50); 0 = none, the reference\'s behaviour. The pool is training-time scratch: '
-                             'it is not written to checkpoints (there is no resume-training path)')
+                             'images (Zhu et al. 2017 use 50); 0 = none, the reference\'s behaviour. The pools, state and contents, are '
+                             'written to checkpoints with the rest of the training state (--resume)')
     add_prediction_flags(parser, image='image', resized=' (the reference)',
                          metrics="cycle-consistency quality, computed on the GPU in inference mode (SSIM as tf.image.ssim, PSNR, MAE of "
                                  "F(G(x)) and F(x) against x, G(F(y)) and G(y) against y): --train writes logs/val_quality.json (per "

@@ -17,7 +17,7 @@ from .base_gan import GAN
 from .diffaug import DiffAugment, parse_policies
 from .quality import QualityMeter, image_quality, summary
 from .steps import Pix2PixStep
-from .runner import (add_common_flags, add_prediction_flags, check_common_flags, check_prediction_flags, drive, finite_lists,
+from .runner import (RESUME_SLOTS, add_common_flags, add_prediction_flags, check_common_flags, check_prediction_flags, drive, finite_lists,
                      save_panels, tile_overlap_of)
 from .utils import pix2pix_losses
 
@@ -192,7 +192,8 @@ class Pix2Pix(GAN):
                 return line
         return self._fit(output_path, checkpoint_manager, pix2pix_losses(), lambda: train_ds, lambda: val_ds, len(train_ds),
                          ('Generator Total Loss', 'Discriminator Loss'),
-                         lambda path: self.generate_images(self.generator, example_input[:1], example_target[:1], path), after_epoch)
+                         lambda path: self.generate_images(self.generator, example_input[:1], example_target[:1], path), after_epoch,
+                         datasets=(train_ds, val_ds, test_ds))
 
     def predict(self, predict_ds, output_path: str):
         """config['predict_training'] 'true' (default): the reference's batch-1 `generator(x, training=True)` per image.  'false':
@@ -256,7 +257,7 @@ class Options(argparse.Namespace):
     """The parsed Pix2Pix command line.  --diffaugment is this driver's own training option: it lives in a slot beside the flag
     dictionary (vars(opt) stays the set of flags the two drivers are compared on) and reaches the model's config - and
     config.json - through runner.config_of."""
-    __slots__ = ('diffaugment',)
+    __slots__ = ('diffaugment',) + RESUME_SLOTS
 
 
 def parse_opt(argv=None):

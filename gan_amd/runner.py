@@ -21,6 +21,7 @@ import torch
 
 from . import ddp
 from .checkpoint import Checkpoint, CheckpointManager, latest_checkpoint
+from .train_state import NAME as TRAIN_STATE, check_resume
 
 
 class Run:
@@ -88,6 +89,12 @@ def check_lr_decay_flags(parser, args) -> None:
         parser.error(f"--lr-end-factor {args.lr_end_factor} is outside [0, 1]")
 
 
+# --resume / --checkpoint-every are declared for both drivers by add_common_flags, and both option classes keep
+# them in slots beside the flag dictionary, as they keep their own training options: vars(opt) stays the set of flags the two
+# drivers are compared on, and config_of hands the slots to the model's config.
+RESUME_SLOTS = ('resume', 'checkpoint_every')
+
+
 def add_common_flags(parser, argv, generator: str, networks: str) -> None:
     """The flags both drivers take: the reference's common ones (pix2pix.py:341-377, cycle_gan.py:379-414) and this project's.
     argv: --epochs is required with --train, --weights with --predict.  generator / networks: the model's nouns for the help
@@ -129,6 +136,13 @@ def add_common_flags(parser, argv, generator: str, networks: str) -> None:
     parser.add_argument('--predict-weights', type=str, default='raw', choices=['raw', 'ema'],
                         help="--predict: 'raw' = the checkpoint's generator weights; 'ema' = its averaged weights (a run with --ema-decay)")
     add_lr_decay_flags(parser)
+    parser.add_argument('--resume', type=str, default=None, metavar='PATH',
+                        help='--train: continue an interrupted run bit for bit from a checkpoint of it: a training_checkpoints directory '
+                             '(its latest checkpoint) or a prefix .../ckpt-N. The run writes a new run directory and continues behind the '
+                             "checkpoint's epoch; everything that shapes the trajectory must be given as in the interrupted run")
+    parser.add_argument('--checkpoint-every', type=int, default=5,
+                        help='--train: write a checkpoint (and a sample image) after every N-th epoch and after the last one '
+                             '(default 5, the reference)')
     parser.add_argument('--device', type=str, default='cuda:0')
     parser.add_argument('--dist-backend', type=str, default='nccl', choices=['nccl', 'gloo'],
                         help='under torchrun (one process per GPU): collective backend; nccl = RCCL over xGMI')
@@ -175,6 +189,10 @@ def check_common_flags(parser, args) -> None:
     if not 0.0 <= args.ema_decay < 1.0:
         parser.error(f"--ema-decay {args.ema_decay} is outside [0, 1)")
     check_lr_decay_flags(parser, args)
+    if args.resume is not None and not args.train:
+        parser.error("--resume continues a training run: it belongs to --train, not to --predict (which takes --weights)")
+    if args.checkpoint_every < 1:
+        parser.error(f"--checkpoint-every {args.checkpoint_every} is less than 1")
     assert (args.img_size == 256) or (args.img_size == 512), "img-size currently only supported for 256 x 256 or 512 x 512 pixels!"
     assert (args.validation_size > 0.0 and args.validation_size <= 0.3), "validation size is a proportion and bounded between 0-0.3!"
     assert (args.test_img >= 1), "test-img is an integer and must be >=1!"
@@ -232,15 +250,21 @@ def plot_loss_curves(train: dict, val: dict, model_name: str, out_dir: str) -> N
 
 
 def run_epochs(epochs: int, keys, train_batches, val_batches, step, on_checkpoint, on_sample, headline, epoch_mean=None, after_pass=None,
-               after_epoch=None):
+               after_epoch=None, checkpoint_every: int = 5, hist=None, resumed_after: int = 0):
     """Epoch driver.  train_batches()/val_batches() yield the positional arguments of `step(*args, training)`, which
     returns the per-step loss tensors (device); `headline` = (train key, val key) printed per epoch.
     epoch_mean(acc, n) -> mean loss vector of a pass (data-parallel runs: over all ranks' steps, gan_amd.ddp.mean_over_ranks).
     after_epoch(epoch) -> None or one more line for the epoch print; runs after the validation pass (image-quality metrics).
+    checkpoint_every: a checkpoint after every N-th epoch and after the last one; the sample image of an epoch follows its checkpoint,
+    except after the last.  hist: the two history dicts to append to (a resumed run: they hold the epochs before).
+    resumed_after: E > 0 continues a run whose state was restored from the checkpoint written after epoch E - behind that
+    checkpoint, so with the sample image that followed it (drawing it moves BatchNorm's moving statistics), then epochs E + 1 ...
     Returns (train_cost_functions, val_cost_functions): {key: [epoch mean, ...]}."""
-    hist = {k: [] for k in keys}, {k: [] for k in keys}
+    hist = hist if hist is not None else ({k: [] for k in keys}, {k: [] for k in keys})
     t0 = time.time()
-    for epoch in range(1, epochs + 1):
+    if 0 < resumed_after < epochs and resumed_after % checkpoint_every == 0:
+        on_sample(resumed_after)
+    for epoch in range(resumed_after + 1, epochs + 1):
         sums = []
         for batches, training in ((train_batches, True), (val_batches, False)):
             acc, n = None, 0
@@ -259,7 +283,7 @@ def run_epochs(epochs: int, keys, train_batches, val_batches, step, on_checkpoin
                 h[k].append(v)
         extra = after_epoch(epoch) if after_epoch is not None else None
         last = epoch == epochs
-        if epoch % 5 == 0 or last:
+        if epoch % checkpoint_every == 0 or last:
             on_checkpoint()
             if not last:
                 on_sample(epoch)
@@ -288,6 +312,12 @@ def drive(opt, model_class, name: str, *, strict_logs: bool, max_to_keep: int, c
     files under logs/ after training, written before the final images (Pix2Pix's image-quality metrics)."""
     info = ddp.init_from_env(opt.device, opt.dist_backend)
     opt.device = info.device or opt.device
+    # --resume is refused before the run directory exists and before anything is built on the GPU (SystemExit, the offending key named)
+    try:
+        resume_from = check_resume(opt.resume, config_of(opt), info.world) if opt.train and getattr(opt, 'resume', None) else None
+    except BaseException:
+        ddp.shutdown(info, failed=True)
+        raise
     run = Run(opt.output, log_to_file=opt.logging == 'true' and info.is_main, strict_logs=strict_logs, writer=info.is_main)
     try:
         model = model_class(config_of(opt))
@@ -296,7 +326,11 @@ def drive(opt, model_class, name: str, *, strict_logs: bool, max_to_keep: int, c
         objects = {n: getattr(model, n) for n in checkpoint_names}
         # after the generators: restore runs in this order, and an average that finds no weights of its own starts over from theirs
         objects.update({avg.model.obj_name + '_ema': avg for avg in model.averages})
+        objects[TRAIN_STATE] = model.train_state      # what a later --resume continues from
         checkpoint = Checkpoint(**objects)
+        if resume_from is not None:
+            checkpoint.restore(resume_from)
+            print(f"Resuming behind epoch {model.train_state.epoch} of {resume_from}", flush=True)
         run.write_json('config.json', model.config)
         if opt.predict:
             if info.is_main:

@@ -24,7 +24,7 @@ TABLE_MAGIC = 0xdb4775248b80fb57
 BLOCK_SIZE, RESTART_INTERVAL = 262144, 16
 # tensorflow/core/framework/types.proto
 DT = {np.dtype('float32'): 1, np.dtype('float64'): 2, np.dtype('int32'): 3, np.dtype('uint8'): 4, np.dtype('int64'): 9,
-      np.dtype('bool'): 10, np.dtype('float16'): 19}
+      np.dtype('bool'): 10, np.dtype('uint16'): 17, np.dtype('float16'): 19, np.dtype('uint32'): 22, np.dtype('uint64'): 23}
 DT_STRING = 7
 DT_INV = {v: k for k, v in DT.items()}
 OBJECT_GRAPH_KEY = '_CHECKPOINTABLE_OBJECT_GRAPH'
