@@ -123,6 +123,13 @@ class GanDssimDesc(_Desc):
                 ("scale_state", C.c_void_p)]
 
 
+class GanEdgeDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("dtype_a", C.c_int32), ("dtype_b", C.c_int32), ("a", GanTensor), ("b", GanTensor),
+                ("loss_scale", C.c_float), ("loss_accumulate", C.c_int32), ("loss_out", C.c_void_p), ("grad_scale", C.c_float),
+                ("dtype_da", C.c_int32), ("da", GanTensor), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("scale_state", C.c_void_p), ("grad_accumulate", C.c_int32)]
+
+
 class GanTileGatherDesc(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("src", C.c_void_p), ("src_bytes", C.c_int64),
                 ("src_pitch", C.c_int32), ("col0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32),
@@ -237,6 +244,8 @@ SYMBOLS = {
     "gan_image_quality": (C.c_int, [C.POINTER(GanQualityDesc), C.c_void_p]),
     "gan_dssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gan_dssim": (C.c_int, [C.POINTER(GanDssimDesc), C.c_void_p]),
+    "gan_edge_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gan_edge_l1": (C.c_int, [C.POINTER(GanEdgeDesc), C.c_void_p]),
     "gan_tile_grid": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gan_tile_gather_u8": (C.c_int, [C.POINTER(GanTileGatherDesc), C.c_void_p]),
     "gan_tile_gather": (C.c_int, [C.POINTER(GanTileGatherFDesc), C.c_void_p]),

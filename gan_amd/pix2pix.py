@@ -38,6 +38,18 @@ def _dssim_eager(a, b):
     return 1.0 - (lum * cs).mean()
 
 
+def _edge_eager(a, b):
+    """The Sobel edge term of two NHWC batches: the eager torch restatement of gan_edge_l1 - the mean of
+    (|Sx * d| + |Sy * d|) / 16 over the valid positions of d = a - b, differentiable through autograd."""
+    d = (a.float() - b.float()).permute(0, 3, 1, 2)
+    c = d.shape[1]
+    sx = torch.tensor([[-1., 0., 1.], [-2., 0., 2.], [-1., 0., 1.]], device=d.device)
+    win = lambda k: k.expand(c, 1, 3, 3).contiguous()
+    ex = torch.nn.functional.conv2d(d, win(sx), groups=c)          # (conv2d correlates, as the definition does)
+    ey = torch.nn.functional.conv2d(d, win(sx.t()), groups=c)
+    return (ex.abs() + ey.abs()).mean() / 16.0
+
+
 class Pix2Pix(GAN):
     def __init__(self, config):
         super().__init__(config)
@@ -105,6 +117,9 @@ class Pix2Pix(GAN):
         assert kind in ('l1', 'dssim'), "the secondary generator loss is 'l1' or 'dssim' ('ssim' is refused by parse_opt)"
         target = torch.as_tensor(target, device=self.ctx.device).float()
         gan_loss2 = _dssim_eager(gen_output, target) if kind == 'dssim' else (target - gen_output).abs().mean()
+        edge_weight = float(self.config.get('edge_weight') or 0.0)
+        if edge_weight > 0.0:               # --edge-weight: a second term in the secondary slot
+            gan_loss2 = gan_loss2 + edge_weight * _edge_eager(gen_output, target)
         return gan_loss + (self.config['lambda'] * gan_loss2), gan_loss, gan_loss2
 
     def _diffaug_for(self, training):
@@ -122,7 +137,8 @@ class Pix2Pix(GAN):
                            lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
                            seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net),
                            generator_loss=self.config.get('generator_loss', 'l1'), gan_loss=self.config.get('gan_loss', 'bce'),
-                           lr_schedule=self.lr_schedule if training else None, diffaug=self._diffaug_for(training))
+                           lr_schedule=self.lr_schedule if training else None, diffaug=self._diffaug_for(training),
+                           edge_weight=float(self.config.get('edge_weight') or 0.0))
 
     def train_step(self, input_image, target, training: bool = True):
         """-> (gen_total_loss, gen_gan_loss, gen_gan_loss2, disc_loss) as 0-d device tensors (no host sync)."""
@@ -254,10 +270,10 @@ class Pix2Pix(GAN):
 
 
 class Options(argparse.Namespace):
-    """The parsed Pix2Pix command line.  --diffaugment is this driver's own training option: it lives in a slot beside the flag
+    """The parsed Pix2Pix command line.  --diffaugment and --edge-weight are this driver's own training options: they live in slots beside the flag
     dictionary (vars(opt) stays the set of flags the two drivers are compared on) and reaches the model's config - and
     config.json - through runner.config_of."""
-    __slots__ = ('diffaugment',) + RESUME_SLOTS
+    __slots__ = ('diffaugment', 'edge_weight') + RESUME_SLOTS
 
 
 def parse_opt(argv=None):
@@ -273,6 +289,10 @@ def parse_opt(argv=None):
                         help="differentiable augmentation of everything the discriminator sees in training steps (Zhao et al. 2020), "
                              "for small datasets: a comma-separated subset of translation,cutout,brightness,saturation; default: none "
                              "(the reference)")
+    parser.add_argument('--edge-weight', type=float, default=0.0,
+                        help="weight W of a Sobel edge term added to the secondary generator loss, relative to --lambda: the generator "
+                             "minimises gan + lambda * (secondary + W * mean |Sobel(generated - target)|); default 0: no edge term "
+                             "(the reference)")
     parser.add_argument('--input-img-orient', type=str, default='left', choices=['left', 'right'], help='whether input image is on left (i.e. target right) or vice-versa')
     parser.add_argument('--lambda', type=int, default=100, help='lambda value for secondary generator loss (L1 / dSSIM)')
     add_prediction_flags(parser, image='half', resized=' (the reference)',
@@ -287,6 +307,8 @@ def parse_opt(argv=None):
         parser.error("--generator-loss ssim is not supported by gan_amd (the reference's SSIM term compares input with target and "
                      "carries no gradient, pix2pix.py:182-184); use the default --generator-loss l1, or --generator-loss dssim "
                      "for 1 - SSIM(generated, target)")
+    if not args.edge_weight >= 0.0 or args.edge_weight == float('inf'):
+        parser.error(f"--edge-weight {args.edge_weight} must be a finite weight >= 0")
     try:
         args.diffaugment = ','.join(parse_policies(args.diffaugment))        # (canonical order: what config.json records)
     except ValueError as e:

@@ -310,9 +310,11 @@ class Pix2PixStep(_StepBase):
 
     def __init__(self, ctx: Ctx, batch, size, channels=1, lam=100.0, lr=2e-4, beta_1=0.5, beta_2=0.999,
                  seed=123, dropout=True, nets=None, mask_stream=0, generator_loss='l1', gan_loss='bce', lr_schedule=None,
-                 diffaug=None):
+                 diffaug=None, edge_weight=0.0):
         if generator_loss not in ('l1', 'dssim'):
             raise ValueError(f"generator_loss {generator_loss!r}: 'l1' or 'dssim'")
+        if not edge_weight >= 0.0:
+            raise ValueError(f"edge_weight {edge_weight!r}: a weight >= 0")
         super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=8, gan_loss=gan_loss)
         self.generator_loss = generator_loss       # the secondary term (losses[2]): mean |target - gen|, or 1 - mean SSIM
         if generator_loss == 'dssim':
@@ -320,6 +322,14 @@ class Pix2PixStep(_StepBase):
             if not need:
                 raise ValueError(f"generator_loss 'dssim': unsupported shape {(batch, size, size, channels)}")
             self.dssim_ws = torch.zeros(need // 4, dtype=torch.float32, device=ctx.device)
+        # a second term in the secondary slot: losses[2] = secondary + edge_weight * Sobel edge term, its
+        # gradient added into g.dgen behind the secondary loss's; 0: the term's launches are not enqueued at all
+        self.edge_weight = float(edge_weight)
+        if self.edge_weight > 0.0:
+            need = ctx.lib.gan_edge_workspace_bytes(batch, size, size, channels)
+            if not need:
+                raise ValueError(f"edge_weight: unsupported shape {(batch, size, size, channels)}")
+            self.edge_ws = torch.zeros(need // 4, dtype=torch.float32, device=ctx.device)
         if nets is not None:          # share weights with an existing step / model objects
             self.G, self.D = nets
         else:
@@ -348,6 +358,14 @@ class Pix2PixStep(_StepBase):
         d = L.GanDssimDesc(ctx.dt, ctx.dt, a, b, loss_scale, int(acc), self.losses.data_ptr() + 4 * loss_idx, grad_scale, ctx.dt,
                            da if da is not None else L.GanTensor(), self.dssim_ws.data_ptr(), self.dssim_ws.numel() * 4, ctx.ls_ptr)
         L.check(ctx.lib.gan_dssim(C.byref(d), stream.cuda_stream if stream is not None else ctx.stream()), "dssim")
+
+    def _edge(self, a, b, loss_idx, loss_scale, acc, grad_scale, da, grad_acc, stream=None):
+        """gan_edge_l1 with _l1's contract, and grad_acc: da += grad_scale * d/da instead of da = ..."""
+        ctx = self.ctx
+        d = L.GanEdgeDesc(ctx.dt, ctx.dt, a, b, loss_scale, int(acc), self.losses.data_ptr() + 4 * loss_idx, grad_scale, ctx.dt,
+                          da if da is not None else L.GanTensor(), self.edge_ws.data_ptr(), self.edge_ws.numel() * 4, ctx.ls_ptr,
+                          int(grad_acc))
+        L.check(ctx.lib.gan_edge_l1(C.byref(d), stream.cuda_stream if stream is not None else ctx.stream()), "edge_l1")
 
     def _settle_gen_options(self):
         """The options of G's call that shape its backward op lists, taken from this object's switches when the first list is
@@ -429,6 +447,9 @@ class Pix2PixStep(_StepBase):
             side.wait_stream(main)
         secondary = self._dssim if self.generator_loss == 'dssim' else self._l1
         secondary(g.out_view(), raw.view(Cc, Cc, 0, B), 2, 1.0, False, self.lam, g.dgen.view(0, Cc), stream=side)
+        if self.edge_weight > 0.0:          # losses[2] += w * edge, g.dgen += lam * w * d edge / d gen: same stream, same operands
+            self._edge(g.out_view(), raw.view(Cc, Cc, 0, B), 2, self.edge_weight, True, self.lam * self.edge_weight, g.dgen.view(0, Cc),
+                       True, stream=side)
         if aug is not None:
             aug.apply(g.out_view(), d.xin.view(Cc, Cc, B, B), Cc, B)
         else:

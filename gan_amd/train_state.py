@@ -28,7 +28,9 @@ CONFIG_KEYS = ('batch_size', 'img_size', 'channels', 'dtype', 'seed', 'learning_
                'generator_loss', 'diffaugment', 'pool_size', 'ema_decay', 'ema_warmup', 'lr_decay_epochs', 'lr_end_factor', 'data_cache',
                'validation_size', 'test_img', 'input_img_orient')
 PATH_KEYS = ('data', 'input_images', 'target_images')
-_DEFAULTS = {'diffaugment': '', 'pool_size': 0, 'ema_decay': 0.0, 'lr_decay_epochs': 0, 'lr_end_factor': 0.0, 'gan_loss': 'bce',
+# run-defining keys that joined after checkpoints were first written: a stored config without one holds its default
+LATER_KEYS = ('edge_weight',)
+_DEFAULTS = {'edge_weight': 0.0, 'diffaugment': '', 'pool_size': 0, 'ema_decay': 0.0, 'lr_decay_epochs': 0, 'lr_end_factor': 0.0, 'gan_loss': 'bce',
              'data_cache': 'host', 'ema_warmup': 'true', 'dtype': 'bf16', 'seed': 123}
 
 
@@ -55,7 +57,7 @@ def _canonical(key, value):
 
 def run_config(config) -> dict:
     """The run-defining part of a model's config (JSON-ready)."""
-    out = {k: _canonical(k, config.get(k)) for k in CONFIG_KEYS + PATH_KEYS}
+    out = {k: _canonical(k, config.get(k)) for k in CONFIG_KEYS + PATH_KEYS + LATER_KEYS}
     out['epochs'] = None if config.get('epochs') is None else int(config['epochs'])
     return out
 
@@ -68,6 +70,10 @@ def check_config(stored: dict, config) -> None:
     for k in CONFIG_KEYS + PATH_KEYS:
         if stored.get(k) != now[k]:
             raise ResumeRefused(f"--resume: {k} differs from the checkpoint's run: stored {stored.get(k)!r}, this run {now[k]!r}")
+    for k in LATER_KEYS:
+        was = _canonical(k, stored.get(k))
+        if was != now[k]:
+            raise ResumeRefused(f"--resume: {k} differs from the checkpoint's run: stored {was!r}, this run {now[k]!r}")
     was, is_ = stored.get('epochs'), now['epochs']
     if was is not None and is_ is not None and was != is_:
         if now['lr_decay_epochs']:

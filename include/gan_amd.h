@@ -677,6 +677,49 @@ size_t gan_dssim_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c);
  * before anything is launched. */
 int gan_dssim(const GanDssimDesc* d, gan_stream_t stream);
 
+/* ---- Sobel edge term of the generator loss --------------------------------------------------------- */
+/* Mean absolute Sobel response of the difference image, and its gradient with respect to a (the prediction); DESIGN.md section 22.
+ * No counterpart in the reference.  d = a - b in fp32 from the stored values; Sx = [[-1,0,1],[-2,0,2],[-1,0,1]], Sy = Sx^T, applied
+ * as correlation at the valid positions q only (1 <= qy <= h-2, 1 <= qx <= w-2: nothing is padded or reflected), M = (h-2)(w-2):
+ *   ex(q) = (Sx * d)(q) / 8,   ey(q) = (Sy * d)(q) / 8,
+ *   loss = sum over images, channels and valid q of (|ex(q)| + |ey(q)|) / (2 n c M),
+ *   dloss/da(p) = k(p) / (16 n c M),
+ *   k(p) = sum over the valid q with |q - p|_inf <= 1 of Sx(p - q) sgn(ex(q)) + Sy(p - q) sgn(ey(q)),   sgn(0) = 0,
+ * an integer in [-16, 16]; a pixel on the image's edge receives only the positions that exist.
+ * Rounding order of the gradient: g = (float(k) * F) / float(n) with the ONE precomputed factor F = (float)(grad_scale / (16 c M))
+ * (the batch-1 coefficient: the quotient in double from the fp32 grad_scale, rounded once), then g = g * scale_state[0] when
+ * scale_state is given; the product, the quotient and the second product are each rounded to fp32 on their own.  So an image's
+ * gradient at batch n is its batch-1 gradient divided by n, rounded once, as gan_dssim's.  grad_accumulate = 0: da = dtype_da(g).  grad_accumulate = 1: da = dtype_da(float(da_old) + g), one
+ * fp32 addition, one rounding to the storage type.  Loss: per (image, tile) one fp32 partial sum of |ex| + |ey|, the partials added
+ * in a fixed order in double, loss_out[0] (+)= (float)(sum / (2 n c M)) * loss_scale.
+ * Two launches: one workgroup per (image, 32 x 32 tile of pixels) stages d with a 2-pixel halo in LDS, forms the two sign maps on
+ * the tile plus 1, writes (or updates) every da element exactly once from its owner thread and writes one fp32 partial to the
+ * workspace; then one fixed-order sum.  No atomics, bit-identical from call to call, enqueue-only, capturable, allocates nothing.
+ * An image's gradient does not depend on the rest of the batch other than through the division by n. */
+typedef struct GanEdgeDesc {
+  uint32_t struct_size;
+  int32_t dtype_a;             /* GAN_F32 | GAN_BF16 | GAN_F16: storage of a */
+  int32_t dtype_b;             /* the same for b */
+  GanTensor a;                 /* prediction: c = 1 or 3, own pitch; only the c real channels are read (pads may hold NaN) */
+  GanTensor b;                 /* target: same n, h, w, c; own dtype and pitch */
+  float loss_scale;
+  int32_t loss_accumulate;     /* 0 | 1 */
+  float* loss_out;             /* device: loss_out[0] (+)= loss_scale * loss, as gan_l1 */
+  float grad_scale;
+  int32_t dtype_da;            /* storage of da */
+  GanTensor da;                /* ptr NULL: loss only.  Same n, h, w, c as a, own pitch; only the c real channels are read and written */
+  void* workspace;             /* device: >= gan_edge_workspace_bytes(n, h, w, c), 4-byte aligned */
+  size_t workspace_bytes;
+  const float* scale_state;    /* fp16 loss scaling, as every loss entry point (the gradient only); NULL = none */
+  int32_t grad_accumulate;     /* 0: da = g;  1: da = round(float(da) + g) - a second term on a gradient another loss wrote */
+} GanEdgeDesc;
+/* 0 for a shape gan_edge_l1 refuses */
+size_t gan_edge_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c);
+/* GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype, c not 1 or 3, n / h / w / c of a, b (and da) differ, n < 1, pitch < c,
+ * loss_accumulate or grad_accumulate not 0 or 1.  GAN_E_SHAPE: h or w below 3 or above 4096.  GAN_E_WORKSPACE: workspace too small.
+ * All found before anything is launched. */
+int gan_edge_l1(const GanEdgeDesc* d, gan_stream_t stream);
+
 /* ---- tiled inference: cut an image into overlapping network-sized tiles, blend the predictions back ------------------ */
 /* Prediction at the source resolution (no counterpart in the reference, which resizes every image to img_size x img_size first,
  * pix2pix.py:43-52): an h x w image is cut into overlapping tile x tile pieces, the pieces go through one inference call as a
