@@ -23,7 +23,16 @@ image-side buffers whose padding channels are not bit-zero.
 
 Wide sweeps (tests/test_gpu_wide_audit.py): captured_step() is the body it shares with tests/test_gpu_launch_audit.py (build, capture,
 reset_step, lattice inputs), outside_classes() the predicate of the calls whose plan class no earlier case has audited,
-missing_classes() names the classes a case was added for that none of its checked rows holds."""
+missing_classes() names the classes a case was added for that none of its checked rows holds.
+
+Option-carrying steps (tests/test_gpu_option_audit.py; dSSIM, the Sobel edge term, DiffAugment, least-squares GAN loss, the learning-rate
+schedule, CycleGAN's image pools): option_step() builds, captures and resets such a step beside captured_step(); OptionStart puts the
+option state (DiffAugment table and counter, pools, mask counters, lr_now and the schedule's counter, loss scale) at a known start;
+the checkers of gan_dssim, gan_edge_l1, gan_diffaug_draw, gan_diffaug_apply, gan_lsq_logits, gan_patchgan_losses_lsq,
+gan_pool_exchange and gan_adam_begin_sched each split into a thin generator that reads the device and a device-free *_ratios function,
+which tests/test_cpu_option_audit.py puts right and planted wrong results through; option_call() is the predicate of the calls such
+an audit checks, same_as_plain() the rule by which the unchecked rest earns AS_ONE_GPU, issue() the unchecked serial re-issue the
+captured graph is compared with."""
 from __future__ import annotations
 
 import contextlib
@@ -959,6 +968,8 @@ def plan_of(call):
         return "acc" if a[3] else ""
     if n == 'gan_bn_fold_multi':
         return f"{a[1]} entries, {a[2]} tiles"
+    if n in OPTION_PLANS:
+        return OPTION_PLANS[n](call)
     return ''
 
 
@@ -1283,6 +1294,577 @@ def _short(sym):
         return sym
     n = int(m.group(1))
     return sym[m.end():m.end() + n]
+
+
+# ---- the option entry points: dSSIM, Sobel edge term, DiffAugment, least-squares GAN loss, image pools, learning-rate schedule ------
+# Each checker is a thin generator (decode the descriptor / argument list the product code built, read the operands through their
+# GanTensor views, yield, read back) around a device-free *_ratios function: (snapshot, descriptor fields, outputs) -> {item: error /
+# gate}.  tests/test_cpu_option_audit.py puts the references' own results and planted faults through the same functions.
+# No gate is new.  Where a stand-alone gate presumes inputs the step does not give it, the derivation stands next to the gate.
+DTN = {L.F32: 'f32', L.BF16: 'bf16', L.F16: 'f16'}
+OPTION_ENTRIES = ('gan_dssim', 'gan_edge_l1', 'gan_diffaug_draw', 'gan_diffaug_apply', 'gan_lsq_logits', 'gan_patchgan_losses_lsq',
+                  'gan_pool_exchange', 'gan_adam_begin_sched')
+EDGE_MARGIN = 1e-5                   # tests/test_gpu_edge.py::general_pair: no contributing Sobel response within this of the kink of |.|
+EDGE_SHARE = 0.01                    # ... ::test_general_cases: at most this share of the elements may be excluded (on the reference alone)
+EDGE_LOSS_REL = 2048 * 2.0 ** -24    # ... the bound of an fp32 tile partial of non-negative terms, relative to the term
+DSSIM_KIND = 'noise'                 # tests/test_gpu_quality.py::SSIM_GATE: an untrained generator's output against a lattice-noise target
+
+
+def ulp32(v):
+    return float(np.spacing(np.float32(abs(float(v)))))
+
+
+def _void(p):
+    """A ctypes pointer argument / field as an integer address (0 for NULL)."""
+    return int(getattr(p, 'value', p) or 0)
+
+
+def tensor_key(t):
+    return (_void(t.ptr), t.n, t.h, t.w, t.c, t.pitch)
+
+
+class Pixels:
+    """Snapshot of the WHOLE pixels a GanTensor view lies in: raw [n, h, w, pitch] of the storage type, and the view's channel offset
+    c0 inside a pixel, taken from the pointer (the step's image-side buffers are pitch-aligned allocations whose samples are whole
+    pixels apart) - so that the channels beside the view, on both sides, are compared too."""
+
+    def __init__(self, t, dt):
+        es = TDT[dt].itemsize
+        self.t, self.dt, self.c = t, dt, t.c
+        self.c0 = (_void(t.ptr) // es) % t.pitch
+        assert self.c0 + t.c <= t.pitch, ("a view that is not inside one pitch-aligned pixel", tensor_key(t))
+        self.raw = read(_void(t.ptr) - self.c0 * es, t.n * t.h * t.w * t.pitch, dt).reshape(t.n, t.h, t.w, t.pitch)
+
+    def real(self):
+        return self.raw[..., self.c0:self.c0 + self.c]
+
+
+def pixels_outside(raw0, raw1, c0, c):
+    """Gate entry: every stored element of the pixels outside channels [c0, c0 + c) keeps its bits (pad channels, and the channels
+    of a neighbouring view)."""
+    keep = torch.ones(raw0.shape[-1], dtype=torch.bool)
+    keep[c0:c0 + c] = False
+    return 0.0 if torch.equal(_bits(raw0[..., keep]), _bits(raw1[..., keep])) else math.inf
+
+
+def _scale_word(ptr):
+    return float(read(ptr, 1)[0]) if ptr else None
+
+
+def dssim_ratios(a, b, da0, da1, c0, loss0, loss1, f):
+    """gan_dssim.  a, b: the stored operands [n,h,w,c]; da0 / da1: whole pixels of da before / after; loss0 / loss1: loss_out before /
+    after; f: loss_scale, loss_accumulate, grad_scale, ls (the loss-scale word or None), dtype_da.
+    Gates of tests/test_gpu_dssim.py: the gradient max|got - want| / max|want| <= 8 * yardstick + ulp(dtype_da), the yardstick being
+    the same reference in float32 against the fp64 one on these very operands; the loss within SSIM_GATE.  da = grad_scale * ls *
+    dloss/da; the loss is NOT multiplied by ls.  loss_accumulate: one more fp32 addition, half an ulp32 of the sum, taken as one."""
+    from tests import dssim_ref
+    from tests.test_gpu_dssim import ULP as DSSIM_ULP
+    from tests.test_gpu_quality import SSIM_GATE
+    c = a.shape[-1]
+    a64, b64 = a.double().numpy(), b.double().numpy()
+    loss, g64 = dssim_ref.loss_and_grad(a64, b64)
+    _, g32 = dssim_ref.loss_and_grad(a64, b64, torch.float32)
+    g64 = g64.numpy()
+    top = float(np.abs(g64).max())
+    yard = float(np.abs(g32.double().numpy() - g64).max() / top) if top > 0 else 0.0
+    k = f['grad_scale'] * (f['ls'] if f['ls'] is not None else 1.0)
+    got = da1[..., c0:c0 + c].double().numpy()
+    res = {}
+    if not np.isfinite(got).all():
+        res['da'] = math.inf
+    else:
+        res['da'] = E_r(float(np.abs(got - k * g64).max()) / (abs(k) * top), 8 * yard + DSSIM_ULP[DTN[f['dtype_da']]])
+    acc = int(f['loss_accumulate'])
+    want = f['loss_scale'] * loss + (float(loss0) if acc else 0.0)
+    res['loss'] = E_r(abs(float(loss1) - want), abs(f['loss_scale']) * SSIM_GATE[DSSIM_KIND] + acc * ulp32(want))
+    res['da untouched outside the view'] = pixels_outside(da0, da1, c0, c)
+    return res
+
+
+def E_r(err, gate):
+    from tests import elementwise_ref as E
+    return E._r(err, gate)
+
+
+def edge_ratios(a, b, da0, da1, c0, loss0, loss1, f):
+    """gan_edge_l1.  Arguments as dssim_ratios; f also holds grad_accumulate.
+    Gradient: bit-equal to the header's rounding order on the reference's integer map k (tests/test_gpu_edge.py::expected_grad:
+    (float(k) * F) / n [* ls], [float(da before) +], ONE rounding to storage - with grad_accumulate the snapshot of da taken before
+    the call), on the elements the reference can decide: no contributing Sobel response within EDGE_MARGIN of 0.  The excluded share
+    is a property of the reference alone and must stay <= EDGE_SHARE.
+    Loss: loss_out (+)= (float)(sum / (2 n c M)) * loss_scale.  The term within EDGE_LOSS_REL of itself (that test's gate, which covers
+    the two roundings of the quotient and the product: 2^-23 against 2^-13); loss_accumulate adds one fp32 addition: half an ulp32
+    of the sum, taken as one."""
+    from tests import edge_ref
+    from tests.test_gpu_edge import bits, expected_grad
+    c = a.shape[-1]
+    a64, b64 = a.double().numpy(), b.double().numpy()
+    k = edge_ref.k_map(a64, b64)
+    mask = edge_ref.min_response(a64, b64) >= EDGE_MARGIN
+    res = {'excluded share / 1 %': float(1.0 - mask.mean()) / EDGE_SHARE}
+    old = da0[..., c0:c0 + c] if f['grad_accumulate'] else None
+    want = expected_grad(k, f['grad_scale'], tuple(a.shape), DTN[f['dtype_da']], ls=f['ls'], old=old)
+    m = torch.from_numpy(mask)
+    got = da1[..., c0:c0 + c].contiguous()
+    res['da (bits)'] = 0.0 if torch.equal(bits(got)[m], bits(want)[m]) else math.inf
+    acc = int(f['loss_accumulate'])
+    term = f['loss_scale'] * edge_ref.loss(a64, b64)
+    want_l = term + (float(loss0) if acc else 0.0)
+    res['loss'] = E_r(abs(float(loss1) - want_l), EDGE_LOSS_REL * abs(term) + acc * ulp32(want_l))
+    res['da untouched outside the view'] = pixels_outside(da0, da1, c0, c)
+    return res
+
+
+def _loss_desc_fields(d):
+    return dict(loss_scale=float(d.loss_scale), loss_accumulate=int(d.loss_accumulate), grad_scale=float(d.grad_scale),
+                ls=_scale_word(d.scale_state), dtype_da=d.dtype_da, grad_accumulate=int(getattr(d, 'grad_accumulate', 0)))
+
+
+def _loss_plan(call):
+    d = call.args[0]._obj
+    return f"{d.a.n}x{d.a.h}x{d.a.w}x{d.a.c} loss x{d.loss_scale:g}{' acc' if d.loss_accumulate else ''} grad x{d.grad_scale:g}" + \
+        (' acc' if getattr(d, 'grad_accumulate', 0) else '') + (' ls' if d.scale_state else '')
+
+
+def _check_image_loss(call, ratios):
+    d = call.args[0]._obj
+    call.plan = _loss_plan(call)
+    assert d.da.ptr, "the audit checks the gradient-carrying form (the step never calls the loss-only one)"
+    a, b = Pixels(d.a, d.dtype_a).real().clone(), Pixels(d.b, d.dtype_b).real().clone()
+    da0 = Pixels(d.da, d.dtype_da)
+    loss0 = float(read(d.loss_out, 1)[0])
+    f = _loss_desc_fields(d)
+    yield
+    da1 = Pixels(d.da, d.dtype_da)
+    return ratios(a, b, da0.raw, da1.raw, da0.c0, loss0, float(read(d.loss_out, 1)[0]), f)
+
+
+def check_dssim(call):
+    return (yield from _check_image_loss(call, dssim_ratios))
+
+
+def check_edge(call):
+    return (yield from _check_image_loss(call, edge_ratios))
+
+
+AUG_RECORDS = 128                    # gan_amd.diffaug.MAX_RECORDS: the table every DiffAugment object allocates
+
+
+def diffaug_draw_ratios(table0, counter0, table1, counter1, f):
+    """gan_diffaug_draw.  table0 / table1: int32 [records, 8] before / after; counter0 / counter1: the device launch counter;
+    f: n, h, w, policy, seed, stream_id.  Bit for bit: records [0, n) = the reference's draws of launch `counter0`, the counter one
+    higher, the records past n unchanged."""
+    from tests import diffaug_ref as R
+    pol = tuple(p for i, p in enumerate(R.POLICIES) if f['policy'] >> i & 1)
+    n = f['n']
+    ref = R.table(R.draw(f['seed'], int(counter0), f['stream_id'], n, f['h'], f['w'], pol))
+    t0, t1 = np.asarray(table0, dtype=np.int32), np.asarray(table1, dtype=np.int32)
+    return {'table (bits)': 0.0 if np.array_equal(t1[:n], ref) else math.inf,
+            'counter + 1': 0.0 if int(counter1) == int(counter0) + 1 else math.inf,
+            'records past n unchanged': 0.0 if np.array_equal(t1[n:], t0[n:]) else math.inf}
+
+
+def check_diffaug_draw(call):
+    table, n, h, w, policy, seed, stream_id, launches = call.args[:8]
+    call.plan = OPTION_PLANS['gan_diffaug_draw'](call)
+    t0 = read(table, AUG_RECORDS * 8, tdtype=torch.int32).numpy().reshape(AUG_RECORDS, 8)
+    c0 = int(read(launches, 1, tdtype=torch.int32)[0])
+    yield
+    t1 = read(table, AUG_RECORDS * 8, tdtype=torch.int32).numpy().reshape(AUG_RECORDS, 8)
+    return diffaug_draw_ratios(t0, c0, t1, int(read(launches, 1, tdtype=torch.int32)[0]),
+                               dict(n=n, h=h, w=w, policy=policy, seed=seed, stream_id=stream_id))
+
+
+def diffaug_apply_ratios(src, dst0, dst1, c0, records, f):
+    """gan_diffaug_apply, either direction.  src: the stored source view [n,h,w,c]; dst0 / dst1: whole pixels of dst before / after;
+    records: the table as it stands in device memory at the call (diffaug_ref.records); f: group_c, sample0, direction, dtype.
+    Gate: fp32 storage 4 fp32 ulps of the largest term of the element's arithmetic (tests/test_gpu_diffaug.py, forward_terms /
+    transpose_terms).  16-bit storage: that test gates at one storage ulp of the expected value and PRESUMES inputs whose terms do
+    not cancel (_inputs_are_fair), so that the fp32 error stays below the half ulp the rounding leaves free; the step's images do
+    cancel, so the fp32 error is counted instead of presumed: K_ULP * ulp_storage(want) + 4 * ulp32(term) - the storage formula
+    of this file with the stand-alone fp32 bound as its accumulation term.  A sample whose record makes colour the identity has its
+    bits moved: equal, and the fill is +0."""
+    from tests import diffaug_ref as R
+    dtn = DTN[f['dtype']]
+    g, s0, n, c = f['group_c'], f['sample0'], src.shape[0], src.shape[-1]
+    x = src.double()
+    used = records[s0:s0 + n]
+    geo = list(records[:s0]) + [dict(p, brightness=0.0, saturation=1.0) for p in used]
+    ones = np.ones(tuple(x.shape))
+    if f['direction'] == 0:
+        want = R.forward(x, records, g, s0).numpy()
+        term = R.forward_terms(x.numpy(), records, g, s0)
+        live = R.forward_terms(ones, geo, g, s0) > 0
+        moved = np.array([p['brightness'] == 0 and (g == 1 or p['saturation'] == 1) for p in used])
+    else:
+        want = R.transpose(x.numpy(), records, g, s0)
+        term = R.transpose_terms(x.numpy(), records, g, s0)
+        live = R.transpose_terms(ones, geo, g, s0) > 0
+        moved = np.array([g == 1 or p['saturation'] == 1 for p in used])
+    got = dst1[..., c0:c0 + c].double().numpy()
+    res = {}
+    if not np.isfinite(got).all():
+        res['dst'] = math.inf
+    else:
+        gate = 4 * R.ulp(term, 'f32') + (0.0 if dtn == 'f32' else K_ULP * R.ulp(want, dtn))
+        err = np.abs(got - want)
+        res['dst'] = float((err[~moved] / gate[~moved]).max()) if (~moved).any() else 0.0
+        res['dst where bits move'] = 0.0 if not err[moved].any() else math.inf
+    res['fill is +0'] = 0.0 if not (np.signbit(got) | (got != 0))[~live].any() else math.inf
+    res['dst untouched outside the view'] = pixels_outside(dst0, dst1, c0, c)
+    return res
+
+
+def check_diffaug_apply(call):
+    from tests import diffaug_ref as R
+    d = call.args[0]._obj
+    call.plan = OPTION_PLANS['gan_diffaug_apply'](call)
+    src = Pixels(d.src, d.dtype).real().clone()
+    dst0 = Pixels(d.dst, d.dtype)
+    nrec = d.sample0 + d.src.n
+    records = R.records(read(d.params, nrec * 8, tdtype=torch.int32).numpy().reshape(nrec, 8))
+    yield
+    dst1 = Pixels(d.dst, d.dtype)
+    return diffaug_apply_ratios(src, dst0.raw, dst1.raw, dst0.c0, records,
+                                dict(group_c=d.group_c, sample0=d.sample0, direction=d.direction, dtype=d.dtype))
+
+
+def _strided(ptr, count, pitch, dt):
+    """[count, pitch] of the storage type: element i of a gradient row lives at i * pitch (whole pixels: the rows are dlogits buffers)."""
+    return read(ptr, count * pitch, dt).reshape(count, pitch) if ptr else None
+
+
+def lsq_ratios(x, f, loss0, loss1, dx0, dx1):
+    """gan_lsq_logits.  x: fp32 numpy [count]; f: target, loss_scale, loss_accumulate, grad_scale, dtype, ls; dx0 / dx1: [count, pitch]
+    before / after (None: no gradient asked for).  lsgan_ref.check_lsq with its gates unchanged; loss_accumulate = 1: the same loss
+    gate around loss0 + loss_scale * mean, plus the ONE fp32 addition (half an ulp32 of the sum; lsgan_ref.check_accumulate needs the
+    unaccumulated loss of the same call, which a replayed step does not have)."""
+    from tests import lsgan_ref as R
+    ls0 = f['ls'] if f['ls'] is not None else 1.0
+    grad = dx1[:, 0] if dx1 is not None else None
+    if not f['loss_accumulate']:
+        res = R.check_lsq(x, f['target'], f['grad_scale'], ls0, f['dtype'], loss1, grad, f['loss_scale'])
+    else:
+        ref_l, ref_g = R.lsq_ref(x, f['target'], f['grad_scale'] * ls0)
+        want = float(loss0) + f['loss_scale'] * ref_l
+        res = {'loss': E_r(abs(float(loss1) - want), abs(f['loss_scale']) * R.loss_gate('gan_lsq_logits', x.size, ref_l) + 0.5 * ulp32(want))}
+        if grad is not None:
+            res['grad'] = R.grad_ratio(grad, ref_g, f['dtype'])
+    if dx1 is not None:
+        res['dx untouched beside the elements'] = pixels_outside(dx0, dx1, 0, 1)
+    return res
+
+
+def check_lsq_logits(call):
+    from tests import elementwise_ref as E
+    x, count, target, loss_scale, acc, loss_out, grad_scale, dt, dx, pitch, ws, ls_ptr = call.args[:12]
+    call.plan = OPTION_PLANS['gan_lsq_logits'](call)
+    xs = read(x, count).numpy().copy()
+    loss0 = float(read(loss_out, 1)[0])
+    dx0 = _strided(dx, count, pitch, dt)
+    f = dict(target=E.f32c(target), loss_scale=E.f32c(loss_scale), loss_accumulate=int(acc), grad_scale=E.f32c(grad_scale), dtype=dt,
+             ls=_scale_word(ls_ptr))
+    yield
+    return lsq_ratios(xs, f, loss0, float(read(loss_out, 1)[0]), dx0, _strided(dx, count, pitch, dt))
+
+
+def fused_lsq_ratios(real, fake, f, got, grads0, grads1):
+    """gan_patchgan_losses_lsq.  real / fake: fp32 numpy [count]; f: dtype, ls, lam, l1 (the device scalar *l1 before the call);
+    got: the fp32 scalars gan, disc, gen_total; grads0 / grads1: {name: [count, pitch]} before / after.  lsgan_ref.check_fused."""
+    from tests import lsgan_ref as R
+    g = dict(got)
+    for k, t in grads1.items():
+        g[k] = t[:, 0] if t is not None else None
+    res = R.check_fused(real, fake, f['ls'] if f['ls'] is not None else 1.0, f['dtype'], g, lam=f['lam'], l1=f['l1'])
+    for k, t in grads1.items():
+        if t is not None:
+            res[f'{k} untouched beside the elements'] = pixels_outside(grads0[k], t, 0, 1)
+    return res
+
+
+def check_patchgan_lsq(call):
+    from tests import elementwise_ref as E
+    real, fake, count, dt, g_dfake, d_dreal, d_dfake, pitch, lam, l1, gen_total, gan, disc, ws, ls_ptr = call.args[:15]
+    call.plan = OPTION_PLANS['gan_patchgan_losses_lsq'](call)
+    r, fk = read(real, count).numpy().copy(), read(fake, count).numpy().copy()
+    ptrs = dict(g_dfake=g_dfake, d_dreal=d_dreal, d_dfake=d_dfake)
+    g0 = {k: _strided(p, count, pitch, dt) for k, p in ptrs.items()}
+    f = dict(dtype=dt, ls=_scale_word(ls_ptr), lam=E.f32c(lam), l1=float(read(l1, 1)[0]) if l1 else 0.0)
+    yield
+    got = dict(gan=float(read(gan, 1)[0]), disc=float(read(disc, 1)[0]), gen_total=float(read(gen_total, 1)[0]) if gen_total else None)
+    return fused_lsq_ratios(r, fk, f, got, g0, {k: _strided(p, count, pitch, dt) for k, p in ptrs.items()})
+
+
+def pool_ratios(src, pool0, state0, dst0, dst1, c0, pool1, state1, f):
+    """gan_pool_exchange.  src: the stored current images [n,h,w,c]; pool0 / pool1: the pool [capacity,h,w,c] before / after; state0 /
+    state1: the three int32 state words; dst0 / dst1: whole pixels of dst; f: seed, stream_id.  Bits are moved: dst, pool contents
+    and state equal pool_ref.query of the snapshot, the block ticket is back at 0, nothing beside dst's channels changes."""
+    from tests import pool_ref as R
+    c = src.shape[-1]
+    out, pool, (stored, launches), trace = R.query(_bits(src).numpy(), _bits(pool0).numpy(), (int(state0[0]), int(state0[1])),
+                                                  f['seed'], f['stream_id'])
+    return {'dst (bits)': 0.0 if np.array_equal(_bits(dst1[..., c0:c0 + c]).numpy(), out) else math.inf,
+            'pool (bits)': 0.0 if np.array_equal(_bits(pool1).numpy(), pool) else math.inf,
+            'state': 0.0 if [int(v) for v in state1] == [stored, launches, 0] else math.inf,
+            'dst untouched outside the view': pixels_outside(dst0, dst1, c0, c)}, trace
+
+
+def check_pool_exchange(call):
+    d = call.args[0]._obj
+    call.plan = OPTION_PLANS['gan_pool_exchange'](call)
+    src = Pixels(d.src, d.dtype).real().clone()
+    shape = (d.capacity, d.src.h, d.src.w, d.src.c)
+    pool0 = read(d.pool, int(np.prod(shape)), d.dtype).reshape(shape)
+    state0 = read(d.state, 3, tdtype=torch.int32).tolist()
+    dst0 = Pixels(d.dst, d.dtype)
+    yield
+    dst1 = Pixels(d.dst, d.dtype)
+    res, trace = pool_ratios(src, pool0, state0, dst0.raw, dst1.raw, dst0.c0, read(d.pool, int(np.prod(shape)), d.dtype).reshape(shape),
+                             read(d.state, 3, tdtype=torch.int32).tolist(), dict(seed=d.seed, stream_id=d.stream_id))
+    call.trace = trace
+    return res
+
+
+def adam_begin_sched_ratios(step0, lr_t0, lr_now0, skip, step1, lr_t1, lr_now1, f):
+    """gan_adam_begin_sched.  step / lr_t / lr_now before and after (np.float32 scalars, lr_now None where the call passes NULL); skip:
+    the loss scale's non-finite flag at the call; f: lr, end_factor, decay_start, decay_end, beta1, beta2.  A skipped step keeps all
+    three, bit for bit; otherwise t = step0 + 1 is stored and both rates are within lr_schedule_ref.GATE_ULPS of the reference."""
+    from tests import lr_schedule_ref as S
+    same = lambda a, b: 0.0 if (a is None and b is None) or np.float32(a).view(np.uint32) == np.float32(b).view(np.uint32) else math.inf
+    if skip:
+        return {'step kept': 0.0 if int(step1) == int(step0) else math.inf, 'lr_t kept': same(lr_t0, lr_t1), 'lr_now kept': same(lr_now0, lr_now1)}
+    t = int(step0) + 1
+    res = {'step + 1': 0.0 if int(step1) == t else math.inf}
+    for k, v in S.check(f['lr'], f['end_factor'], f['decay_start'], f['decay_end'], f['beta1'], f['beta2'], t, lr_t1, lr_now1).items():
+        res[k] = v / S.GATE_ULPS
+    return res
+
+
+def check_adam_begin_sched(call):
+    step, lr_t, lr_now, s, b1, b2, ls_ptr = call.args[:7]
+    s = s._obj
+    call.plan = OPTION_PLANS['gan_adam_begin_sched'](call)
+    rd = lambda: (int(read(step, 1, tdtype=torch.int32)[0]), read(lr_t, 1).numpy()[0], read(lr_now, 1).numpy()[0] if lr_now else None)
+    before = rd()
+    skip = bool(ls_ptr) and float(read(ls_ptr, 4)[3]) != 0.0
+    yield
+    return adam_begin_sched_ratios(*before, skip, *rd(), dict(lr=s.lr, end_factor=s.end_factor, decay_start=s.decay_start,
+                                                               decay_end=s.decay_end, beta1=b1, beta2=b2))
+
+
+def _aug_plan(call):
+    d = call.args[0]._obj
+    return f"{'backward' if d.direction else 'forward'} {d.src.n}x{d.src.h}x{d.src.w}x{d.src.c} group {d.group_c} sample0 {d.sample0}"
+
+
+def _pool_plan(call):
+    d = call.args[0]._obj
+    return f"{d.src.n}x{d.src.h}x{d.src.w}x{d.src.c} capacity {d.capacity} stream {d.stream_id}"
+
+
+def _sched_plan(call):
+    s = call.args[3]._obj
+    return f"decay [{s.decay_start}, {s.decay_end}) to x{s.end_factor:g}"
+
+
+# plan strings from the descriptor / argument list alone (plan_of)
+OPTION_PLANS = {
+    'gan_dssim': _loss_plan, 'gan_edge_l1': _loss_plan, 'gan_diffaug_apply': _aug_plan, 'gan_pool_exchange': _pool_plan,
+    'gan_adam_begin_sched': _sched_plan,
+    'gan_diffaug_draw': lambda c: f"{c.args[1]} records {c.args[2]}x{c.args[3]} policy {c.args[4]:#x} stream {c.args[6]}",
+    'gan_lsq_logits': lambda c: f"count {c.args[1]} target {c.args[2]:g} loss x{c.args[3]:g}{' acc' if c.args[4] else ''} grad x{c.args[6]:g}"
+                                + (' ls' if c.args[11] else ''),
+    'gan_patchgan_losses_lsq': lambda c: f"count {c.args[2]} lambda {c.args[8]:g}" + (' ls' if c.args[14] else ''),
+}
+CHECKERS.update(gan_dssim=check_dssim, gan_edge_l1=check_edge, gan_diffaug_draw=check_diffaug_draw, gan_diffaug_apply=check_diffaug_apply,
+                gan_lsq_logits=check_lsq_logits, gan_patchgan_losses_lsq=check_patchgan_lsq, gan_pool_exchange=check_pool_exchange,
+                gan_adam_begin_sched=check_adam_begin_sched)
+
+
+# ---- which calls an option audit checks, and how the rest earns AS_ONE_GPU ----------------------------------------------------------
+def _span(ptr, elems, es):
+    return (_void(ptr), _void(ptr) + elems * es)
+
+
+def _tensor_span(t, es):
+    rows = t.n * t.h * t.w
+    return _span(t.ptr, (rows - 1) * t.pitch + t.c if rows else 0, es)
+
+
+def option_regions(step):
+    """Address ranges of the buffers only an option creates: aug_raw and aug_dgen of a DiffAugment step; with image pools the pooled
+    third (samples B .. 2B-1) of every forward buffer of both discriminators' three-invocation calls."""
+    reg = []
+    rng = lambda t: (t.data_ptr(), t.data_ptr() + t.numel() * t.element_size())
+    if getattr(step, 'diffaug', None) is not None:
+        reg += [rng(step.aug_raw.t), rng(step.aug_dgen.t)]
+    if getattr(step, 'pools', None):
+        B = step.B
+        for d in (step.dx, step.dy):
+            for buf in [d.xin, d.logits] + list(d.y.values()) + list(d.a.values()):
+                reg.append(rng(buf.t[B:2 * B]))
+    return reg
+
+
+def option_call(regions):
+    """Predicate of replay(check=...): the option entry points, and every conv / dgrad / wgrad call with an operand in `regions`."""
+    def hit(t, dt):
+        a, b = _tensor_span(t, TDT[dt].itemsize)
+        return any(a < hi and lo < b for lo, hi in regions)
+
+    def check(call):
+        if call.name in OPTION_ENTRIES:
+            return True
+        if call.name in OPS:
+            d = call.args[0]._obj
+            return hit(d.x, d.dtype) or hit(d.y, L.F32 if d.y_f32 else d.dtype)
+        if call.name == 'gan_conv_wgrad':
+            d = call.args[0]._obj
+            return hit(d.big, d.dtype) or hit(d.small, d.dtype)
+        return False
+    return check
+
+
+OPTION_MAP = {'gan_lsq_logits': 'gan_bce_logits', 'gan_patchgan_losses_lsq': 'gan_patchgan_losses', 'gan_adam_begin_sched': 'gan_adam_begin',
+              'gan_dssim': 'gan_l1'}          # an option entry point that stands in the place of a plain one, argument for argument
+OPTION_STRUCK = ('gan_edge_l1', 'gan_diffaug_draw', 'gan_diffaug_apply', 'gan_pool_exchange')       # ... that the plain step has no call for
+ANY = 'checked'              # the key of a call the audit checks itself: its plan class need not be the plain step's
+
+
+def same_as_plain(option, plain, replaced_copy=None):
+    """The rule by which the unchecked calls of an option step carry AS_ONE_GPU.  option / plain: [(entry point, key)] in recorded
+    order; key = the plan class of a conv / wgrad call (call_class), None for every other entry point, ANY for a call the audit
+    checks.  Strike OPTION_STRUCK from the option list, map the entry points of OPTION_MAP back (tests/test_gpu_lsgan.py::
+    test_launch_lists; gan_dssim stands where gan_l1 stood), strike from the plain list the one gan_copy_view that
+    gan_diffaug_apply replaces (its index: replaced_copy): the two sequences must then be equal, entry for entry.
+    -> the differences as strings (empty: the rule holds)."""
+    a = [(OPTION_MAP.get(n, n), k) for n, k in option if n not in OPTION_STRUCK]
+    b = list(plain)
+    if replaced_copy is not None:
+        assert b[replaced_copy][0] == 'gan_copy_view', b[replaced_copy]
+        del b[replaced_copy]
+    bad = []
+    if len(a) != len(b):
+        bad.append(f"{len(a)} calls left of the option step, {len(b)} of the plain one")
+    for i, ((n1, k1), (n2, k2)) in enumerate(zip(a, b)):
+        if n1 != n2 or (k1 != ANY and k1 != k2):
+            bad.append(f"position {i}: option step {n1} {k1}, plain step {n2} {k2}")
+            if len(bad) >= 8:
+                break
+    return bad
+
+
+def sequence_of(calls, check=None):
+    """[(entry point, key)] of recorded calls for same_as_plain: check = the audit's predicate (None: the plain step, every class kept)."""
+    return [(c.name, ANY if check is not None and check(c) else call_class(c)) for c in calls]
+
+
+def issue(calls, stream=None):
+    """The recorded calls re-issued one by one, in recorded order, on one stream, unchecked (the serial order a captured graph's
+    dependency edges must be equivalent to)."""
+    st = (stream or torch.cuda.current_stream()).cuda_stream
+    for c in calls:
+        rc = c.fn(*c.args[:-1], st)
+        if rc:
+            L.check(rc, f"{c.name} ({c.label})")
+    torch.cuda.synchronize()
+
+
+# ---- the option-carrying step, built as captured_step builds the plain one -----------------------------------------------------------
+POOL_CAPACITY = 3
+AUG_LAUNCH0 = 5              # the DiffAugment launch counter at the known start (not 0: the counter must be READ)
+AUG_FILL = 0x5A5A5A5A        # what every table record holds before the draw
+SCHED_STEP0 = 2              # the step counters of a scheduled step at the known start: update index 2 of STEP_SCHEDULE runs at lr / 2
+
+
+def lattice(shape, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, 256, tuple(shape), generator=g).float() / 127.5 - 1.0
+
+
+def pool_launches(batch, capacity, seed, stream_id, want):
+    """The smallest launch counter at which a full pool's query decides `want` ('swap' / 'keep') for its first image."""
+    from tests import pool_ref
+    for k in range(1, 256):
+        if pool_ref.decisions(batch, capacity, seed, stream_id, capacity, k)[0][0][0] == want:
+            return k
+    raise AssertionError(want)
+
+
+class OptionStart:
+    """Puts an option step at its known start: reset_step (unchanged), then every tensor of DiffAugment.tensors(), every tensor of
+    each ImagePool.tensors() - full pools of lattice images, pool_y at a launch counter where its first image is swapped, pool_x
+    where it is kept, so that the two exchanges of a step take both branches - the mask_draws counters, lr_now and the step counters
+    of a scheduled step, the loss-scale state, and the lattice inputs."""
+
+    def __init__(self, step, saved, replay_, inputs, ls0):
+        self.step, self.saved, self.replay, self.inputs, self.ls0 = step, saved, replay_, inputs, ls0
+
+    def __call__(self):
+        st = self.step
+        reset_step(st, self.saved)
+        for net in st.nets():
+            P = net.params
+            if P.lr_schedule is not None:
+                P.step.fill_(SCHED_STEP0)
+                P.lr_now.fill_(float(P.lr_schedule.lr))
+        for call in vars(st).values():
+            if hasattr(call, 'mask_draws'):
+                call.mask_draws.zero_()
+        aug = getattr(st, 'diffaug', None)
+        if aug is not None:
+            launches, table = aug.tensors()
+            launches.fill_(AUG_LAUNCH0)
+            table.fill_(AUG_FILL)
+        for i, pool in enumerate(getattr(st, 'pools', None) or ()):
+            state, storage = pool.tensors()
+            storage.copy_(lattice(storage.shape, 31 + i).to(storage.dtype))
+            k = pool_launches(st.B, pool.capacity, pool.seed, pool.stream_id, ('swap', 'keep')[i])
+            state.copy_(torch.tensor([pool.capacity, k, 0], dtype=torch.int32))
+        if self.ls0 is not None:
+            st.ctx.ls.copy_(self.ls0)
+        for t, src in zip(self.replay.inputs, self.inputs):
+            t.copy_(src)
+        torch.cuda.synchronize()
+
+
+def option_step(model, dtype, channels, batch, monkeypatch, size=256, generator_loss='l1', edge_weight=0.0, diffaug=None, gan_loss='bce',
+                lr_schedule=None, pools=None):
+    """captured_step with the option keywords and `channels`: recorder first, then build, capture, reset.  diffaug: the policies
+    (a comma-separated string) or None; lr_schedule: (decay_start, decay_end, end_factor) or None; pools: the capacity or None.
+    -> (step, labelled calls, the captured replay, the OptionStart that was just run)."""
+    import gc
+    from gan_amd.diffaug import DiffAugment
+    from gan_amd.nets import Ctx, LrSchedule, workspace_mb_for
+    from gan_amd.pool import STREAM_X, STREAM_Y, ImagePool
+    from gan_amd.steps import CycleGANStep, Pix2PixStep
+    gc.collect()                                  # (graphs of the previous case: see captured_step)
+    torch.cuda.synchronize()
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    rec = Recorder(monkeypatch)
+    rec.hook_capture(monkeypatch)
+    ctx = Ctx('cuda:0', dtype, workspace_mb=workspace_mb_for(batch, size, channels, calls=3 if pools else 2))
+    ls0 = ctx.ls.clone() if ctx.ls is not None else None
+    sched = LrSchedule(2e-4, lr_schedule[2], lr_schedule[0], lr_schedule[1]) if lr_schedule else None
+    if model == 'pix2pix':
+        assert pools is None
+        aug = DiffAugment(ctx, diffaug, seed=123) if diffaug else None
+        st = Pix2PixStep(ctx, batch, size, channels, lam=100.0, seed=123, generator_loss=generator_loss, gan_loss=gan_loss,
+                         lr_schedule=sched, diffaug=aug, edge_weight=edge_weight)
+    else:
+        assert generator_loss == 'l1' and not edge_weight and diffaug is None
+        pl = (ImagePool(ctx, size, channels, pools, 123, STREAM_Y), ImagePool(ctx, size, channels, pools, 123, STREAM_X)) if pools else None
+        st = CycleGANStep(ctx, batch, size, channels, lam=10.0, seed=123, gan_loss=gan_loss, lr_schedule=sched, pools=pl)
+    saved = [(n.params.master.clone(), {k: t.clone() for k, t in n.params.state.items()}) for n in st.nets()]
+    replay_ = st.capture(training=True)
+    torch.cuda.synchronize()
+    calls = rec.calls
+    assert calls, "nothing recorded inside the capture body"
+    label_calls(calls, st)
+    inputs = [lattice(t.shape, 7 + batch + 100 * i).to(t.device) for i, t in enumerate(replay_.inputs)]
+    start = OptionStart(st, saved, replay_, inputs, ls0)
+    start()
+    return st, calls, replay_, start
 
 
 # ---- the captured one-GPU step at channels = 1: what tests/test_gpu_launch_audit.py and tests/test_gpu_wide_audit.py replay ----------
