@@ -130,6 +130,26 @@ class GanEdgeDesc(_Desc):
                 ("scale_state", C.c_void_p), ("grad_accumulate", C.c_int32)]
 
 
+MSSSIM_POWER = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # tf.image.ssim_multiscale's default power factors
+Float5 = C.c_float * 5                                        # `float power[5]` (tools/gen_binding.py names array members so)
+
+
+class GanMsssimDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("dtype_a", C.c_int32), ("dtype_b", C.c_int32), ("a", GanTensor), ("b", GanTensor),
+                ("loss_scale", C.c_float), ("loss_accumulate", C.c_int32), ("loss_out", C.c_void_p), ("grad_scale", C.c_float),
+                ("dtype_da", C.c_int32), ("da", GanTensor), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("scale_state", C.c_void_p), ("scales", C.c_int32), ("power", Float5), ("per_image", C.c_void_p),
+                ("grad_accumulate", C.c_int32)]
+
+
+def msssim_power(scales, power=None):
+    """-> ctypes float[5]: `power` (a sequence of `scales` factors) or the first `scales` default factors."""
+    p = tuple(MSSSIM_POWER[:scales] if power is None else power)
+    if not 1 <= scales <= 5 or len(p) != scales:
+        raise ValueError(f"msssim: {scales} scales with {len(p)} power factors (1 .. 5 scales, one factor each)")
+    return Float5(*p)
+
+
 class GanTileGatherDesc(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("dtype", C.c_int32), ("src", C.c_void_p), ("src_bytes", C.c_int64),
                 ("src_pitch", C.c_int32), ("col0", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("c", C.c_int32),
@@ -246,6 +266,8 @@ SYMBOLS = {
     "gan_dssim": (C.c_int, [C.POINTER(GanDssimDesc), C.c_void_p]),
     "gan_edge_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gan_edge_l1": (C.c_int, [C.POINTER(GanEdgeDesc), C.c_void_p]),
+    "gan_msssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gan_msssim": (C.c_int, [C.POINTER(GanMsssimDesc), C.c_void_p]),
     "gan_tile_grid": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gan_tile_gather_u8": (C.c_int, [C.POINTER(GanTileGatherDesc), C.c_void_p]),
     "gan_tile_gather": (C.c_int, [C.POINTER(GanTileGatherFDesc), C.c_void_p]),

@@ -38,6 +38,37 @@ def _dssim_eager(a, b):
     return 1.0 - (lum * cs).mean()
 
 
+MSSSIM_POWER = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def _msssim_eager(a, b, power=MSSSIM_POWER):
+    """1 - mean MS-SSIM(a, b) of two NHWC batches in [-1, 1]: the eager torch restatement of gan_msssim (DESIGN.md section 24;
+    tf.image.ssim_multiscale on the display range with max_val 1): per level the map means of cs (of lum * cs on the last), the
+    next level the 2 x 2 mean with the last row / column repeated where a side is odd, the product of the clamped means raised to
+    `power` per image and channel; differentiable through autograd."""
+    ua, ub = (0.5 * t.float().permute(0, 3, 1, 2) + 0.5 for t in (a, b))
+    c = ua.shape[1]
+    k = torch.arange(11, dtype=torch.float64, device=ua.device) - 5
+    g = torch.exp(-k * k / (2 * 1.5 ** 2))
+    g = (g / g.sum()).float()
+    win = (g[:, None] * g[None, :]).expand(c, 1, 11, 11).contiguous()
+    F = lambda t: torch.nn.functional.conv2d(t, win, groups=c)
+    pool = lambda t: torch.nn.functional.avg_pool2d(torch.nn.functional.pad(t, (0, t.shape[3] % 2, 0, t.shape[2] % 2), mode='replicate'), 2)
+    ms = None
+    for j, w in enumerate(power):
+        mx, my = F(ua), F(ub)
+        term = (2 * (F(ua * ub) - mx * my) + 9e-4) / (F(ua * ua + ub * ub) - mx * mx - my * my + 9e-4)
+        if j == len(power) - 1:
+            term = term * (2 * mx * my + 1e-4) / (mx * mx + my * my + 1e-4)
+        m = term.mean(dim=(2, 3))
+        pos = m > 0                  # the clamped region has gradient 0 by definition
+        f = torch.where(pos, torch.where(pos, m, torch.ones_like(m)) ** w, torch.zeros_like(m))
+        ms = f if ms is None else ms * f
+        if j + 1 < len(power):
+            ua, ub = pool(ua), pool(ub)
+    return 1.0 - ms.mean(dim=1).mean()
+
+
 def _edge_eager(a, b):
     """The Sobel edge term of two NHWC batches: the eager torch restatement of gan_edge_l1 - the mean of
     (|Sx * d| + |Sy * d|) / 16 over the valid positions of d = a - b, differentiable through autograd."""
@@ -113,10 +144,19 @@ class Pix2Pix(GAN):
     # ---- losses / step (pix2pix.py:167-218) ------------------------------------------------------
     def generator_loss(self, disc_generated_output, gen_output, target, input_image):
         gan_loss = self.loss_obj(1.0, disc_generated_output)
-        kind = self.config['generator_loss']
-        assert kind in ('l1', 'dssim'), "the secondary generator loss is 'l1' or 'dssim' ('ssim' is refused by parse_opt)"
+        kind = str(self.config['generator_loss']).replace('-', '_')
+        assert kind in ('l1', 'dssim', 'msssim', 'msssim_l1'), \
+            "the secondary generator loss is 'l1', 'dssim', 'msssim' or 'msssim-l1' ('ssim' is refused by parse_opt)"
         target = torch.as_tensor(target, device=self.ctx.device).float()
-        gan_loss2 = _dssim_eager(gen_output, target) if kind == 'dssim' else (target - gen_output).abs().mean()
+        if kind == 'dssim':
+            gan_loss2 = _dssim_eager(gen_output, target)
+        elif kind == 'msssim':
+            gan_loss2 = _msssim_eager(gen_output, target)
+        elif kind == 'msssim_l1':       # Zhao et al. 2017: (1 - alpha) L1 + alpha (1 - MS-SSIM)
+            alpha = float(self.config.get('msssim_alpha') or 0.84)
+            gan_loss2 = (1.0 - alpha) * (target - gen_output).abs().mean() + alpha * _msssim_eager(gen_output, target)
+        else:
+            gan_loss2 = (target - gen_output).abs().mean()
         edge_weight = float(self.config.get('edge_weight') or 0.0)
         if edge_weight > 0.0:               # --edge-weight: a second term in the secondary slot
             gan_loss2 = gan_loss2 + edge_weight * _edge_eager(gen_output, target)
@@ -136,7 +176,8 @@ class Pix2Pix(GAN):
         return Pix2PixStep(self.ctx, batch, self.config['img_size'], int(self.config['channels']), lam=self.config['lambda'],
                            lr=self.config['learning_rate'], beta_1=self.config['beta_1'], beta_2=self.config['beta_2'],
                            seed=int(self.config.get('seed', 123)), mask_stream=0 if training else 16, nets=(self.generator.net, self.discriminator.net),
-                           generator_loss=self.config.get('generator_loss', 'l1'), gan_loss=self.config.get('gan_loss', 'bce'),
+                           generator_loss=str(self.config.get('generator_loss', 'l1')).replace('-', '_'),
+                           msssim_alpha=float(self.config.get('msssim_alpha') or 0.84), gan_loss=self.config.get('gan_loss', 'bce'),
                            lr_schedule=self.lr_schedule if training else None, diffaug=self._diffaug_for(training),
                            edge_weight=float(self.config.get('edge_weight') or 0.0))
 
@@ -270,10 +311,10 @@ class Pix2Pix(GAN):
 
 
 class Options(argparse.Namespace):
-    """The parsed Pix2Pix command line.  --diffaugment and --edge-weight are this driver's own training options: they live in slots beside the flag
+    """The parsed Pix2Pix command line.  --diffaugment, --edge-weight and --msssim-alpha are this driver's own training options: they live in slots beside the flag
     dictionary (vars(opt) stays the set of flags the two drivers are compared on) and reaches the model's config - and
     config.json - through runner.config_of."""
-    __slots__ = ('diffaugment', 'edge_weight') + RESUME_SLOTS
+    __slots__ = ('diffaugment', 'edge_weight', 'msssim_alpha') + RESUME_SLOTS
 
 
 def parse_opt(argv=None):
@@ -282,9 +323,14 @@ def parse_opt(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument('--data', type=str, help='path to data', required=True)
     add_common_flags(parser, argv, generator='the generator', networks='generator and discriminator')
-    parser.add_argument('--generator-loss', type=str, default='l1', choices=['l1', 'ssim', 'dssim'],
+    parser.add_argument('--generator-loss', type=str, default='l1', choices=['l1', 'ssim', 'dssim', 'msssim', 'msssim-l1'],
                         help="secondary generator loss: 'l1' = mean |target - generated|; 'dssim' = 1 - mean SSIM(generated, target), computed "
-                             "with its gradient on the GPU; 'ssim' (the reference's input-against-target term) is refused")
+                             "with its gradient on the GPU; 'msssim' = 1 - mean MS-SSIM(generated, target) over five scales "
+                             "(tf.image.ssim_multiscale's power factors); 'msssim-l1' = (1 - A) * l1 + A * msssim "
+                             "with A = --msssim-alpha; 'ssim' (the reference's input-against-target term) is refused")
+    parser.add_argument('--msssim-alpha', type=float, default=None,
+                        help="mixing weight A of --generator-loss msssim-l1, 0 < A <= 1 (default 0.84, Zhao et al. 2017); refused with any "
+                             "other loss")
     parser.add_argument('--diffaugment', type=str, default='',
                         help="differentiable augmentation of everything the discriminator sees in training steps (Zhao et al. 2020), "
                              "for small datasets: a comma-separated subset of translation,cutout,brightness,saturation; default: none "
@@ -307,6 +353,12 @@ def parse_opt(argv=None):
         parser.error("--generator-loss ssim is not supported by gan_amd (the reference's SSIM term compares input with target and "
                      "carries no gradient, pix2pix.py:182-184); use the default --generator-loss l1, or --generator-loss dssim "
                      "for 1 - SSIM(generated, target)")
+    if args.msssim_alpha is not None and args.generator_loss != 'msssim-l1':
+        parser.error(f"--msssim-alpha belongs to --generator-loss msssim-l1, not to --generator-loss {args.generator_loss}")
+    if args.msssim_alpha is None:
+        args.msssim_alpha = 0.84
+    if not 0.0 < args.msssim_alpha <= 1.0:
+        parser.error(f"--msssim-alpha {args.msssim_alpha} must be a weight in (0, 1]")
     if not args.edge_weight >= 0.0 or args.edge_weight == float('inf'):
         parser.error(f"--edge-weight {args.edge_weight} must be a finite weight >= 0")
     try:

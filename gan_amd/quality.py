@@ -58,6 +58,30 @@ def image_quality(ctx, pred, target, out=None):
     return out
 
 
+def ms_ssim(ctx, pred, target, scales=5, power=None):
+    """-> float32 device tensor [n]: the MS-SSIM of every image (include/gan_amd.h: gan_msssim as a metric - loss only, per_image;
+    DESIGN.md section 24).  Operands as image_quality's; power: `scales` factors (default: tf.image.ssim_multiscale's first
+    `scales`).  Enqueue-only on the current stream; the workspace is cached per shape on the context.  A shape the kernel
+    refuses (a side below 11 * 2^(scales - 1)) raises ValueError."""
+    tb, dtb, keep_b = _operand(ctx, target)
+    ta, dta, keep_a = _operand(ctx, pred, tb.c)
+    n, h, w, c = tb.n, tb.h, tb.w, tb.c
+    pw = L.msssim_power(scales, power)
+    cache = ctx.__dict__.setdefault('_msssim_ws', {})
+    key = (n, h, w, c, scales)
+    if key not in cache:
+        need = ctx.lib.gan_msssim_workspace_bytes(n, h, w, c, scales)
+        if not need:
+            raise ValueError(f"ms_ssim: unsupported shape {(n, h, w, c)} for {scales} scales")
+        cache[key] = torch.empty(need // 4 + 1, dtype=torch.float32, device=ctx.device)       # (+ 1: the loss word)
+    ws = cache[key]
+    out = torch.empty((n,), dtype=torch.float32, device=ctx.device)
+    d = L.GanMsssimDesc(dta, dtb, ta, tb, 1.0, 0, ws.data_ptr() + 4 * (ws.numel() - 1), 0.0, L.F32, L.GanTensor(), ws.data_ptr(),
+                        (ws.numel() - 1) * 4, None, scales, pw, out.data_ptr(), 0)
+    L.check(ctx.lib.gan_msssim(C.byref(d), ctx.stream()), "msssim")
+    return out
+
+
 class QualityMeter:
     """Per-image rows of a pass, kept on the device: add() never synchronises, drain() makes the one transfer."""
 

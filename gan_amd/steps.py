@@ -310,9 +310,11 @@ class Pix2PixStep(_StepBase):
 
     def __init__(self, ctx: Ctx, batch, size, channels=1, lam=100.0, lr=2e-4, beta_1=0.5, beta_2=0.999,
                  seed=123, dropout=True, nets=None, mask_stream=0, generator_loss='l1', gan_loss='bce', lr_schedule=None,
-                 diffaug=None, edge_weight=0.0):
-        if generator_loss not in ('l1', 'dssim'):
-            raise ValueError(f"generator_loss {generator_loss!r}: 'l1' or 'dssim'")
+                 diffaug=None, edge_weight=0.0, msssim_alpha=0.84):
+        if generator_loss not in ('l1', 'dssim', 'msssim', 'msssim_l1'):
+            raise ValueError(f"generator_loss {generator_loss!r}: 'l1', 'dssim', 'msssim' or 'msssim_l1'")
+        if not 0.0 < msssim_alpha <= 1.0:
+            raise ValueError(f"msssim_alpha {msssim_alpha!r}: a mixing weight in (0, 1]")
         if not edge_weight >= 0.0:
             raise ValueError(f"edge_weight {edge_weight!r}: a weight >= 0")
         super().__init__(ctx, batch, size, channels, lam, lr, beta_1, beta_2, n_losses=8, gan_loss=gan_loss)
@@ -322,6 +324,16 @@ class Pix2PixStep(_StepBase):
             if not need:
                 raise ValueError(f"generator_loss 'dssim': unsupported shape {(batch, size, size, channels)}")
             self.dssim_ws = torch.zeros(need // 4, dtype=torch.float32, device=ctx.device)
+        # 1 - mean MS-SSIM over five scales with tf.image.ssim_multiscale's power factors, alone ('msssim') or
+        # mixed with L1 ('msssim_l1', Zhao et al. 2017): losses[2] = (1 - alpha) L1 + alpha (1 - MS-SSIM)
+        self.msssim_alpha = float(msssim_alpha)
+        if generator_loss in ('msssim', 'msssim_l1'):
+            self.msssim_scales = len(L.MSSSIM_POWER)
+            need = ctx.lib.gan_msssim_workspace_bytes(batch, size, size, channels, self.msssim_scales)
+            if not need:
+                raise ValueError(f"generator_loss {generator_loss!r}: unsupported shape {(batch, size, size, channels)} for "
+                                 f"{self.msssim_scales} scales")
+            self.msssim_ws = torch.zeros(need // 4, dtype=torch.float32, device=ctx.device)
         # a second term in the secondary slot: losses[2] = secondary + edge_weight * Sobel edge term, its
         # gradient added into g.dgen behind the secondary loss's; 0: the term's launches are not enqueued at all
         self.edge_weight = float(edge_weight)
@@ -358,6 +370,20 @@ class Pix2PixStep(_StepBase):
         d = L.GanDssimDesc(ctx.dt, ctx.dt, a, b, loss_scale, int(acc), self.losses.data_ptr() + 4 * loss_idx, grad_scale, ctx.dt,
                            da if da is not None else L.GanTensor(), self.dssim_ws.data_ptr(), self.dssim_ws.numel() * 4, ctx.ls_ptr)
         L.check(ctx.lib.gan_dssim(C.byref(d), stream.cuda_stream if stream is not None else ctx.stream()), "dssim")
+
+    def _msssim(self, a, b, loss_idx, loss_scale, acc, grad_scale, da, stream=None, grad_acc=False):
+        """gan_msssim with _l1's contract: losses[loss_idx] (+)= loss_scale * (1 - mean MS-SSIM(a, b)), da (+)= grad_scale * d/da."""
+        ctx = self.ctx
+        d = L.GanMsssimDesc(ctx.dt, ctx.dt, a, b, loss_scale, int(acc), self.losses.data_ptr() + 4 * loss_idx, grad_scale, ctx.dt,
+                            da if da is not None else L.GanTensor(), self.msssim_ws.data_ptr(), self.msssim_ws.numel() * 4, ctx.ls_ptr,
+                            self.msssim_scales, L.msssim_power(self.msssim_scales), None, int(grad_acc))
+        L.check(ctx.lib.gan_msssim(C.byref(d), stream.cuda_stream if stream is not None else ctx.stream()), "msssim")
+
+    def _msssim_l1(self, a, b, loss_idx, loss_scale, acc, grad_scale, da, stream=None):
+        """(1 - alpha) * gan_l1, and directly behind it on the same stream alpha * gan_msssim added to the loss word and to da."""
+        al = self.msssim_alpha
+        self._l1(a, b, loss_idx, loss_scale * (1.0 - al), acc, grad_scale * (1.0 - al), da, stream=stream)
+        self._msssim(a, b, loss_idx, loss_scale * al, True, grad_scale * al, da, stream=stream, grad_acc=da is not None)
 
     def _edge(self, a, b, loss_idx, loss_scale, acc, grad_scale, da, grad_acc, stream=None):
         """gan_edge_l1 with _l1's contract, and grad_acc: da += grad_scale * d/da instead of da = ..."""
@@ -445,7 +471,7 @@ class Pix2PixStep(_StepBase):
         # forward when lanes are on), then all three BCE terms in one pass
         if side is not None:
             side.wait_stream(main)
-        secondary = self._dssim if self.generator_loss == 'dssim' else self._l1
+        secondary = {'l1': self._l1, 'dssim': self._dssim, 'msssim': self._msssim, 'msssim_l1': self._msssim_l1}[self.generator_loss]
         secondary(g.out_view(), raw.view(Cc, Cc, 0, B), 2, 1.0, False, self.lam, g.dgen.view(0, Cc), stream=side)
         if self.edge_weight > 0.0:          # losses[2] += w * edge, g.dgen += lam * w * d edge / d gen: same stream, same operands
             self._edge(g.out_view(), raw.view(Cc, Cc, 0, B), 2, self.edge_weight, True, self.lam * self.edge_weight, g.dgen.view(0, Cc),

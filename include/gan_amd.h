@@ -720,6 +720,63 @@ size_t gan_edge_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c);
  * All found before anything is launched. */
 int gan_edge_l1(const GanEdgeDesc* d, gan_stream_t stream);
 
+/* ---- multi-scale structural dissimilarity as a training loss (and a metric) ----------------------------- */
+/* MS-SSIM (Wang, Simoncelli, Bovik 2003; tf.image.ssim_multiscale) of a (prediction) against b (target), its loss 1 - mean and
+ * the gradient with respect to a; DESIGN.md section 24.  No counterpart in the reference.
+ * Levels.  M = scales, 1 .. 5.  Level 0 is the stored image; level j + 1 has h' = ceil(h_j / 2), w' = ceil(w_j / 2) and is the
+ * 2 x 2 mean with the last row / column repeated where a side is odd (symmetric padding, then a VALID average pool):
+ *   x_{j+1}(i, k) = 0.25 * ((x_j(2i, 2k) + x_j(2i, k1)) + (x_j(i1, 2k) + x_j(i1, k1))),  i1 = min(2i + 1, h_j - 1),  k1 = min(2k + 1, w_j - 1),
+ * in fp32 in that order on the centred values x' = 0.5 x that gan_dssim stages, by the same operations for a and b.
+ * Shapes.  c = 1 or 3, h, w <= 4096 and h, w >= 11 * 2^(M - 1): every level holds a full window (h_j, w_j >= 11), also where it is
+ * pooled without the repeated edge; anything else is GAN_E_SHAPE.
+ * Per level, image and channel, with gan_dssim's lum = A1 / B1 and cs = A2 / B2 (same window, c1, c2, display range, VALID map):
+ *   CS_j = mean over the map of cs,   S_j = mean over the map of lum * cs,
+ *   MS = prod_{j < M-1} max(CS_j, 0)^power[j] * max(S_{M-1}, 0)^power[M-1],
+ * an image's score is the channel mean of MS (per_image[i] when given) and loss = 1 - mean over the images.  With M = 1 and
+ * power[0] = 1 this is gan_dssim's loss.
+ * Gradient.  k_j = power[j] MS / CS_j (j < M-1), k_{M-1} = power[M-1] MS / S_{M-1}, every k of an image and channel 0 when one of
+ * its factors was clamped.  g_j = dCS_j / d level j (j < M-1): gan_dssim's transposed-filter form with the maps of cs alone, centred,
+ *   P = -(2 / B2) (mb - cs ma),   Q = 2 / B2,   R = -cs / B2;
+ * g_{M-1} = dS_{M-1} / d level M-1 with gan_dssim's own P, Q, R.  G_j = k_j g_j + U(G_{j+1}), U the exact transpose of the pooling
+ * (a pixel receives 0.25 of its parent's value once per time it is one of the parent's four taps), and
+ *   dloss/da = -0.5 G_0 / (n c),
+ * times grad_scale, times scale_state[0] when given.  The value of an image is its batch-1 value divided by n, rounded once.
+ * grad_accumulate = 0: da = dtype_da(g);  1: da = dtype_da(float(da_old) + g), one fp32 addition, one rounding, as gan_edge_l1.
+ * For a == b the loss and every da element are exactly 0.
+ * Launches: M - 1 pooling launches, one statistics launch over the tiles of all levels (fp32 partial sums of cs and lum * cs per
+ * (level, image, channel, 32 x 32 tile) into the workspace), one finalize launch (the partials added in a fixed order in double; MS,
+ * per_image, the k_j and the loss word) - M + 1 launches for the loss alone - and, with da, one gradient launch per level from
+ * the coarsest to level 0: 2 M + 1 in all (11 at M = 5).  Pooled levels, partials, coefficients and the gradients of the levels
+ * above 0 live in the workspace as fp32.  No atomics, bit-identical from call to call, enqueue-only, capturable, allocates
+ * nothing; each da element is written once by its owner thread. */
+typedef struct GanMsssimDesc {
+  uint32_t struct_size;
+  int32_t dtype_a;             /* GAN_F32 | GAN_BF16 | GAN_F16: storage of a */
+  int32_t dtype_b;             /* the same for b */
+  GanTensor a;                 /* prediction: c = 1 or 3, own pitch; only the c real channels are read (pads may hold NaN) */
+  GanTensor b;                 /* target: same n, h, w, c; own dtype and pitch */
+  float loss_scale;
+  int32_t loss_accumulate;     /* 0 | 1 */
+  float* loss_out;             /* device: loss_out[0] (+)= loss_scale * loss, as gan_l1 */
+  float grad_scale;
+  int32_t dtype_da;            /* storage of da */
+  GanTensor da;                /* ptr NULL: loss only.  Same n, h, w, c as a, own pitch; only the c real channels are (read and) written */
+  void* workspace;             /* device: >= gan_msssim_workspace_bytes(n, h, w, c, scales), 4-byte aligned */
+  size_t workspace_bytes;
+  const float* scale_state;    /* fp16 loss scaling, as every loss entry point (the gradient only); NULL = none */
+  int32_t scales;              /* M: 1 .. 5 */
+  float power[5];              /* power[0 .. M-1], finite and >= 0; tf.image.ssim_multiscale: 0.0448, 0.2856, 0.3001, 0.2363, 0.1333 */
+  float* per_image;            /* device [n] or NULL: the score of every image (the call as a metric) */
+  int32_t grad_accumulate;     /* 0: da = g;  1: da = round(float(da) + g) - a second term on a gradient another loss wrote */
+} GanMsssimDesc;
+/* 0 for a shape or a number of scales gan_msssim refuses */
+size_t gan_msssim_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t c, int32_t scales);
+/* GAN_E_ARG: NULL pointer, wrong struct_size, bad dtype, c not 1 or 3, n / h / w / c of a, b (and da) differ, n < 1, pitch < c,
+ * loss_accumulate or grad_accumulate not 0 or 1, scales outside 1 .. 5, a power factor negative or not finite.  GAN_E_SHAPE: h or
+ * w below 11 * 2^(scales - 1) or above 4096.  GAN_E_WORKSPACE: workspace too small.  All found before anything is launched: a
+ * refused call writes nothing. */
+int gan_msssim(const GanMsssimDesc* d, gan_stream_t stream);
+
 /* ---- tiled inference: cut an image into overlapping network-sized tiles, blend the predictions back ------------------ */
 /* Prediction at the source resolution (no counterpart in the reference, which resizes every image to img_size x img_size first,
  * pix2pix.py:43-52): an h x w image is cut into overlapping tile x tile pieces, the pieces go through one inference call as a

@@ -27,6 +27,9 @@ def parse_structs(header=None):
                 star = ptr or ('*' if nm.startswith('*') else '')
                 nm = nm.lstrip('* ')
                 ct = 'C.c_void_p' if star else (CT.get(base) or base)       # struct members keep their struct name
+                arr = re.match(r'(\w+)\[(\d+)\]$', nm)
+                if arr:                                                     # float power[5] -> ("power", Float5): gan_amd/_lib.py names its array types
+                    nm, ct = arr.group(1), f'{base.capitalize()}{arr.group(2)}'
                 fields.append((nm, ct))
         out[m.group(1)] = fields
     return out
