@@ -25,14 +25,15 @@ Wide sweeps (tests/test_gpu_wide_audit.py): captured_step() is the body it share
 reset_step, lattice inputs), outside_classes() the predicate of the calls whose plan class no earlier case has audited,
 missing_classes() names the classes a case was added for that none of its checked rows holds.
 
-Option-carrying steps (tests/test_gpu_option_audit.py; dSSIM, the Sobel edge term, DiffAugment, least-squares GAN loss, the learning-rate
-schedule, CycleGAN's image pools): option_step() builds, captures and resets such a step beside captured_step(); OptionStart puts the
+Option-carrying steps (tests/test_gpu_option_audit.py; dSSIM, MS-SSIM, the Sobel edge term, DiffAugment, least-squares GAN loss, the
+learning-rate schedule, CycleGAN's image pools): option_step() builds, captures and resets such a step beside captured_step(); OptionStart puts the
 option state (DiffAugment table and counter, pools, mask counters, lr_now and the schedule's counter, loss scale) at a known start;
-the checkers of gan_dssim, gan_edge_l1, gan_diffaug_draw, gan_diffaug_apply, gan_lsq_logits, gan_patchgan_losses_lsq,
+the checkers of gan_dssim, gan_msssim, gan_edge_l1, gan_diffaug_draw, gan_diffaug_apply, gan_lsq_logits, gan_patchgan_losses_lsq,
 gan_pool_exchange and gan_adam_begin_sched each split into a thin generator that reads the device and a device-free *_ratios function,
 which tests/test_cpu_option_audit.py puts right and planted wrong results through; option_call() is the predicate of the calls such
 an audit checks, same_as_plain() the rule by which the unchecked rest earns AS_ONE_GPU, issue() the unchecked serial re-issue the
-captured graph is compared with."""
+captured graph is compared with; near_target() gives an MS-SSIM step a target near the generator's own output, the inputs for which
+the loss gate of gan_msssim is derived."""
 from __future__ import annotations
 
 import contextlib
@@ -1296,13 +1297,13 @@ def _short(sym):
     return sym[m.end():m.end() + n]
 
 
-# ---- the option entry points: dSSIM, Sobel edge term, DiffAugment, least-squares GAN loss, image pools, learning-rate schedule ------
+# ---- the option entry points: dSSIM, MS-SSIM, Sobel edge term, DiffAugment, least-squares GAN loss, image pools, learning-rate schedule ------
 # Each checker is a thin generator (decode the descriptor / argument list the product code built, read the operands through their
 # GanTensor views, yield, read back) around a device-free *_ratios function: (snapshot, descriptor fields, outputs) -> {item: error /
 # gate}.  tests/test_cpu_option_audit.py puts the references' own results and planted faults through the same functions.
 # No gate is new.  Where a stand-alone gate presumes inputs the step does not give it, the derivation stands next to the gate.
 DTN = {L.F32: 'f32', L.BF16: 'bf16', L.F16: 'f16'}
-OPTION_ENTRIES = ('gan_dssim', 'gan_edge_l1', 'gan_diffaug_draw', 'gan_diffaug_apply', 'gan_lsq_logits', 'gan_patchgan_losses_lsq',
+OPTION_ENTRIES = ('gan_dssim', 'gan_msssim', 'gan_edge_l1', 'gan_diffaug_draw', 'gan_diffaug_apply', 'gan_lsq_logits', 'gan_patchgan_losses_lsq',
                   'gan_pool_exchange', 'gan_adam_begin_sched')
 EDGE_MARGIN = 1e-5                   # tests/test_gpu_edge.py::general_pair: no contributing Sobel response within this of the kink of |.|
 EDGE_SHARE = 0.01                    # ... ::test_general_cases: at most this share of the elements may be excluded (on the reference alone)
@@ -1415,6 +1416,57 @@ def edge_ratios(a, b, da0, da1, c0, loss0, loss1, f):
     return res
 
 
+MSSSIM_PREMISE = 0.4                 # tests/test_gpu_msssim.py: every factor CS_j, S_{M-1} at least this, the premise of its loss gate
+
+
+def msssim_ratios(a, b, da0, da1, c0, loss0, loss1, f):
+    """gan_msssim.  Arguments as dssim_ratios; f also holds grad_accumulate, scales and power (the descriptor's fp32 factors).
+    Reference: tests/msssim_ref.loss_and_grad in float64 on the stored operands; the same function in float32 is the yardstick.
+    premise: MSSSIM_PREMISE / the reference's smallest factor - a condition on the INPUTS, computed from the reference alone; under it
+      |dMS| <= max_j |dCS_j| / 0.4, which is what makes the loss gate below valid (tests/test_gpu_msssim.py).  Above 1 the row fails:
+      the operands are of a kind the gate is not derived for (independent images: factors at the clamp, where pow is ill-conditioned).
+    da, grad_accumulate = 0: dssim_ratios' form and tests/test_gpu_msssim.py's gate, max|got - k g64| / (|k| max|g64|) <= 8 * yardstick +
+      ulp(dtype_da), k = grad_scale * (the loss-scale word or 1).
+    da, grad_accumulate = 1: the kernel forms the fp32 term t = k g as it does when it stores, widens da before exactly, adds in fp32
+      and rounds the sum ONCE to dtype_da.  |t - k g64| is bounded by the storing form's gate taken absolutely, |k| max|g64| *
+      (8 * yardstick + ulp(dtype_da)) (generous by the one storage rounding of t that this form does not make); the fp32 addition and the
+      rounding to storage together stay within one storage ulp of the wanted sum float(da before) + k g64 (half an ulp for round to
+      nearest, the other half for a sum that sits on the other side of a binade edge, as K_ULP; at fp32 storage the addition IS the
+      rounding).  Per element: |got - wanted| <= |k| max|g64| * (8 * yardstick + ulp(dtype_da)) + ulp_storage(wanted).  No new constant.
+    loss: wanted loss_scale * loss (+ loss0); gate |loss_scale| * 2.5 * SSIM_GATE (the 2.5e-5 of tests/test_gpu_msssim_step.py, valid by
+      the premise row) + one ulp32 of the sum for the accumulating addition.  The loss is NOT multiplied by the loss-scale word."""
+    from tests import msssim_ref
+    from tests.test_gpu_dssim import ULP as DSSIM_ULP
+    from tests.test_gpu_quality import SSIM_GATE
+    c, M = a.shape[-1], int(f['scales'])
+    power = tuple(float(p) for p in f['power'])[:M]
+    a64, b64 = a.double().numpy(), b.double().numpy()
+    loss, g64, _ = msssim_ref.loss_and_grad(a64, b64, M, power)
+    _, g32, _ = msssim_ref.loss_and_grad(a64, b64, M, power, dtype=torch.float32)
+    fmin = msssim_ref.min_factor(a64, b64, M)
+    g64 = g64.numpy()
+    top = float(np.abs(g64).max())
+    yard = float(np.abs(g32.double().numpy() - g64).max() / top) if top > 0 else 0.0
+    k = f['grad_scale'] * (f['ls'] if f['ls'] is not None else 1.0)
+    dt = f['dtype_da']
+    bound = 8 * yard + DSSIM_ULP[DTN[dt]]
+    got = da1[..., c0:c0 + c].double().numpy()
+    res = {'premise': MSSSIM_PREMISE / fmin if fmin > 0 else math.inf}
+    if not np.isfinite(got).all():
+        res['da'] = math.inf
+    elif not f['grad_accumulate']:
+        res['da'] = E_r(float(np.abs(got - k * g64).max()), abs(k) * top * bound)       # (a gradient that is 0 everywhere: 0 demanded)
+    else:
+        want = da0[..., c0:c0 + c].double().numpy() + k * g64
+        gate = abs(k) * top * bound + ulp(torch.from_numpy(want), dt).numpy()
+        res['da'] = float((np.abs(got - want) / gate).max())
+    acc = int(f['loss_accumulate'])
+    want = f['loss_scale'] * loss + (float(loss0) if acc else 0.0)
+    res['loss'] = E_r(abs(float(loss1) - want), abs(f['loss_scale']) * 2.5 * SSIM_GATE[DSSIM_KIND] + acc * ulp32(want))
+    res['da untouched outside the view'] = pixels_outside(da0, da1, c0, c)
+    return res
+
+
 def _loss_desc_fields(d):
     return dict(loss_scale=float(d.loss_scale), loss_accumulate=int(d.loss_accumulate), grad_scale=float(d.grad_scale),
                 ls=_scale_word(d.scale_state), dtype_da=d.dtype_da, grad_accumulate=int(getattr(d, 'grad_accumulate', 0)))
@@ -1426,14 +1478,15 @@ def _loss_plan(call):
         (' acc' if getattr(d, 'grad_accumulate', 0) else '') + (' ls' if d.scale_state else '')
 
 
-def _check_image_loss(call, ratios):
+def _check_image_loss(call, ratios, **more):
+    """more: descriptor fields beyond _loss_desc_fields that `ratios` reads from f."""
     d = call.args[0]._obj
-    call.plan = _loss_plan(call)
+    call.plan = OPTION_PLANS[call.name](call)
     assert d.da.ptr, "the audit checks the gradient-carrying form (the step never calls the loss-only one)"
     a, b = Pixels(d.a, d.dtype_a).real().clone(), Pixels(d.b, d.dtype_b).real().clone()
     da0 = Pixels(d.da, d.dtype_da)
     loss0 = float(read(d.loss_out, 1)[0])
-    f = _loss_desc_fields(d)
+    f = dict(_loss_desc_fields(d), **more)
     yield
     da1 = Pixels(d.da, d.dtype_da)
     return ratios(a, b, da0.raw, da1.raw, da0.c0, loss0, float(read(d.loss_out, 1)[0]), f)
@@ -1445,6 +1498,11 @@ def check_dssim(call):
 
 def check_edge(call):
     return (yield from _check_image_loss(call, edge_ratios))
+
+
+def check_msssim(call):
+    d = call.args[0]._obj
+    return (yield from _check_image_loss(call, msssim_ratios, scales=int(d.scales), power=tuple(d.power)[:d.scales]))
 
 
 AUG_RECORDS = 128                    # gan_amd.diffaug.MAX_RECORDS: the table every DiffAugment object allocates
@@ -1669,14 +1727,15 @@ def _sched_plan(call):
 
 # plan strings from the descriptor / argument list alone (plan_of)
 OPTION_PLANS = {
-    'gan_dssim': _loss_plan, 'gan_edge_l1': _loss_plan, 'gan_diffaug_apply': _aug_plan, 'gan_pool_exchange': _pool_plan,
+    'gan_dssim': _loss_plan, 'gan_msssim': lambda c: _loss_plan(c) + f" M{c.args[0]._obj.scales}", 'gan_edge_l1': _loss_plan,
+    'gan_diffaug_apply': _aug_plan, 'gan_pool_exchange': _pool_plan,
     'gan_adam_begin_sched': _sched_plan,
     'gan_diffaug_draw': lambda c: f"{c.args[1]} records {c.args[2]}x{c.args[3]} policy {c.args[4]:#x} stream {c.args[6]}",
     'gan_lsq_logits': lambda c: f"count {c.args[1]} target {c.args[2]:g} loss x{c.args[3]:g}{' acc' if c.args[4] else ''} grad x{c.args[6]:g}"
                                 + (' ls' if c.args[11] else ''),
     'gan_patchgan_losses_lsq': lambda c: f"count {c.args[2]} lambda {c.args[8]:g}" + (' ls' if c.args[14] else ''),
 }
-CHECKERS.update(gan_dssim=check_dssim, gan_edge_l1=check_edge, gan_diffaug_draw=check_diffaug_draw, gan_diffaug_apply=check_diffaug_apply,
+CHECKERS.update(gan_dssim=check_dssim, gan_msssim=check_msssim, gan_edge_l1=check_edge, gan_diffaug_draw=check_diffaug_draw, gan_diffaug_apply=check_diffaug_apply,
                 gan_lsq_logits=check_lsq_logits, gan_patchgan_losses_lsq=check_patchgan_lsq, gan_pool_exchange=check_pool_exchange,
                 gan_adam_begin_sched=check_adam_begin_sched)
 
@@ -1726,30 +1785,47 @@ def option_call(regions):
 
 
 OPTION_MAP = {'gan_lsq_logits': 'gan_bce_logits', 'gan_patchgan_losses_lsq': 'gan_patchgan_losses', 'gan_adam_begin_sched': 'gan_adam_begin',
-              'gan_dssim': 'gan_l1'}          # an option entry point that stands in the place of a plain one, argument for argument
+              'gan_dssim': 'gan_l1', 'gan_msssim': 'gan_l1'}       # an option entry point that stands in the place of a plain one, argument for argument
 OPTION_STRUCK = ('gan_edge_l1', 'gan_diffaug_draw', 'gan_diffaug_apply', 'gan_pool_exchange')       # ... that the plain step has no call for
 ANY = 'checked'              # the key of a call the audit checks itself: its plan class need not be the plain step's
+# gan_msssim takes one of two places, and the caller says which (same_as_plain(msssim=...), the step's generator_loss): 'msssim' - it
+# stands where gan_l1 stood (OPTION_MAP, as gan_dssim); 'msssim_l1' - gan_l1 stays and gan_msssim is an extra call directly behind it
+# (struck); None - the step has no MS-SSIM loss and must not record the entry point at all.
+MSSSIM_PLACES = (None, 'msssim', 'msssim_l1')
 
 
-def same_as_plain(option, plain, replaced_copy=None):
+def same_as_plain(option, plain, replaced_copy=None, msssim=None):
     """The rule by which the unchecked calls of an option step carry AS_ONE_GPU.  option / plain: [(entry point, key)] in recorded
     order; key = the plan class of a conv / wgrad call (call_class), None for every other entry point, ANY for a call the audit
     checks.  Strike OPTION_STRUCK from the option list, map the entry points of OPTION_MAP back (tests/test_gpu_lsgan.py::
     test_launch_lists; gan_dssim stands where gan_l1 stood), strike from the plain list the one gan_copy_view that
     gan_diffaug_apply replaces (its index: replaced_copy): the two sequences must then be equal, entry for entry.
+    msssim (MSSSIM_PLACES): the place gan_msssim takes.  Striking and mapping alone cannot see a second gan_msssim behind gan_l1 or
+    one that has changed places with the (struck) edge term, so with either place there is exactly one such call, no gan_edge_l1 in
+    front of it, and for 'msssim_l1' the call directly in front of it is gan_l1; without a place there is none.
     -> the differences as strings (empty: the rule holds)."""
-    a = [(OPTION_MAP.get(n, n), k) for n, k in option if n not in OPTION_STRUCK]
+    assert msssim in MSSSIM_PLACES, msssim
+    bad = []
+    at = [i for i, (n, _) in enumerate(option) if n == 'gan_msssim']
+    if len(at) != (msssim is not None):
+        bad.append(f"{len(at)} gan_msssim calls at {at} in a step with generator loss {msssim or 'l1 / dssim'}")
+    for i in at:
+        if any(n == 'gan_edge_l1' for n, _ in option[:i]):
+            bad.append(f"position {i}: gan_msssim behind the edge term")
+        if msssim == 'msssim_l1' and (i == 0 or option[i - 1][0] != 'gan_l1'):
+            bad.append(f"position {i}: gan_msssim of 'msssim_l1' behind {option[i - 1][0] if i else 'nothing'}, not gan_l1")
+    struck = OPTION_STRUCK + (('gan_msssim',) if msssim == 'msssim_l1' else ())
+    a = [(OPTION_MAP.get(n, n), k) for n, k in option if n not in struck]
     b = list(plain)
     if replaced_copy is not None:
         assert b[replaced_copy][0] == 'gan_copy_view', b[replaced_copy]
         del b[replaced_copy]
-    bad = []
     if len(a) != len(b):
         bad.append(f"{len(a)} calls left of the option step, {len(b)} of the plain one")
     for i, ((n1, k1), (n2, k2)) in enumerate(zip(a, b)):
         if n1 != n2 or (k1 != ANY and k1 != k2):
             bad.append(f"position {i}: option step {n1} {k1}, plain step {n2} {k2}")
-            if len(bad) >= 8:
+            if len(bad) >= 12:
                 break
     return bad
 
@@ -1829,9 +1905,10 @@ class OptionStart:
 
 
 def option_step(model, dtype, channels, batch, monkeypatch, size=256, generator_loss='l1', edge_weight=0.0, diffaug=None, gan_loss='bce',
-                lr_schedule=None, pools=None):
+                lr_schedule=None, pools=None, msssim_alpha=0.84):
     """captured_step with the option keywords and `channels`: recorder first, then build, capture, reset.  diffaug: the policies
-    (a comma-separated string) or None; lr_schedule: (decay_start, decay_end, end_factor) or None; pools: the capacity or None.
+    (a comma-separated string) or None; lr_schedule: (decay_start, decay_end, end_factor) or None; pools: the capacity or None;
+    msssim_alpha: the mixing weight of generator_loss 'msssim_l1' (the product's default).
     -> (step, labelled calls, the captured replay, the OptionStart that was just run)."""
     import gc
     from gan_amd.diffaug import DiffAugment
@@ -1847,10 +1924,10 @@ def option_step(model, dtype, channels, batch, monkeypatch, size=256, generator_
     ls0 = ctx.ls.clone() if ctx.ls is not None else None
     sched = LrSchedule(2e-4, lr_schedule[2], lr_schedule[0], lr_schedule[1]) if lr_schedule else None
     if model == 'pix2pix':
-        assert pools is None
+        assert pools is None and generator_loss in ('l1', 'dssim', 'msssim', 'msssim_l1'), (pools, generator_loss)
         aug = DiffAugment(ctx, diffaug, seed=123) if diffaug else None
         st = Pix2PixStep(ctx, batch, size, channels, lam=100.0, seed=123, generator_loss=generator_loss, gan_loss=gan_loss,
-                         lr_schedule=sched, diffaug=aug, edge_weight=edge_weight)
+                         lr_schedule=sched, diffaug=aug, edge_weight=edge_weight, msssim_alpha=msssim_alpha)
     else:
         assert generator_loss == 'l1' and not edge_weight and diffaug is None
         pl = (ImagePool(ctx, size, channels, pools, 123, STREAM_Y), ImagePool(ctx, size, channels, pools, 123, STREAM_X)) if pools else None
@@ -1865,6 +1942,27 @@ def option_step(model, dtype, channels, batch, monkeypatch, size=256, generator_
     start = OptionStart(st, saved, replay_, inputs, ls0)
     start()
     return st, calls, replay_, start
+
+
+NEAR_SEED = 977              # of the lattice noise near_target adds
+
+
+def near_target(step, start, amp):
+    """Give a Pix2Pix option step a target near its generator's own output: the operands gan_msssim's loss gate is derived for
+    (tests/test_gpu_msssim.py: a = clip(b + amp * U); an untrained generator against an independent lattice image has its factors at the
+    clamp).  Pix2Pix's G reads only the un-augmented input x, and start() resets the weights, the norm state and the dropout
+    counters, so G's output at the known start is reproducible and does not depend on the target: start(), one replay, read G's
+    stored output, target = clip(gen + amp * lattice noise, -1, 1) rounded to the 8-bit lattice of the inputs, in start.inputs (so
+    that every later start() restores it), start() again.  Whether the premise holds on the result is the checker's 'premise' row."""
+    start()
+    start.replay(*start.replay.inputs)
+    torch.cuda.synchronize()
+    gen = step.g.output_f32().double().cpu()
+    tar = torch.clamp(gen + amp * lattice(gen.shape, NEAR_SEED).double(), -1.0, 1.0)
+    tar = torch.round((tar + 1.0) * 127.5) / 127.5 - 1.0
+    assert tuple(start.inputs[1].shape) == tuple(tar.shape), (tuple(start.inputs[1].shape), tuple(tar.shape))
+    start.inputs[1] = tar.float().to(start.inputs[1].device)
+    start()
 
 
 # ---- the captured one-GPU step at channels = 1: what tests/test_gpu_launch_audit.py and tests/test_gpu_wide_audit.py replay ----------

@@ -1,4 +1,4 @@
-"""The device-free halves of the option checkers of tests/launch_audit.py (dssim_ratios, edge_ratios, diffaug_draw_ratios,
+"""The device-free halves of the option checkers of tests/launch_audit.py (dssim_ratios, msssim_ratios, edge_ratios, diffaug_draw_ratios,
 diffaug_apply_ratios, lsq_ratios, fused_lsq_ratios, pool_ratios, adam_begin_sched_ratios) on the CPU, on lattice inputs laid out as
 the option-carrying steps lay them out: pitch-8 pixels, the target at channel offset C, f32 / bf16 / f16 at channels 1 and 3.
 
@@ -16,7 +16,10 @@ Must fail: what a wiring or scaling bug of the step would leave in memory -
     element for the 16-bit types - its gate is the stand-alone test's max-norm one, 8 float32 yardsticks + one storage ulp, which at
     fp32 storage is wider than two fp32 ulps by construction);
   - a table drawn with the counter one off;
-  - the pool state advanced without the swap.
+  - the pool state advanced without the swap;
+  - MS-SSIM (test_msssim_compare; 45 x 47 at three scales: odd sides pooled on every level; a = clip(b + 0.1 U), the operands its loss
+    gate is derived for): the above, and the gradient stored where it should accumulate and the reverse, the loss word stored where it
+    should accumulate, the gradient of one level fewer, and independent operands, which must fail the premise row.
 And the rule by which unchecked calls earn "as in the one-GPU step" (same_as_plain) accepts the intended sequence and rejects an extra
 or a reordered launch."""
 import math
@@ -27,7 +30,7 @@ import torch
 
 from gan_amd import _lib as L
 from tests import diffaug_ref as DR
-from tests import dssim_ref, edge_ref, lr_schedule_ref, lsgan_ref, pool_ref
+from tests import dssim_ref, edge_ref, lr_schedule_ref, lsgan_ref, msssim_ref, pool_ref
 from tests import elementwise_ref as E
 from tests import launch_audit as A
 
@@ -89,6 +92,7 @@ def edge_model(a, b, dt, f, old, loss0, ls_in_grad=True, ls_in_loss=False, accum
 
 
 def augmented(b, dt, c):
+    H, W = b.shape[1], b.shape[2]
     recs = DR.draw(123, 5, 48, 2 * B, H, W, ALL)
     return stored(DR.forward(b.double(), recs, c, 0).numpy(), dt)
 
@@ -156,6 +160,87 @@ def test_edge_compare(dt, c):
     idx = tuple(int(v) for v in np.argwhere(mask)[len(np.argwhere(mask)) // 2])
     assert run(bump(da, idx, 2), loss) == ['da (bits)']                                              # a 2-ulp error in one element
     assert run(da, float(np.float32(loss) * np.float32(1.0 + 4096 * 2.0 ** -24))) == ['loss']
+
+
+# ---- MS-SSIM ---------------------------------------------------------------------------------------------------------------------------
+MH, MW, MS = 45, 47, 3               # odd sides on every level (45 x 47, 23 x 24, 12 x 12), the smallest with three
+M_AMP = 0.1                          # tests/test_gpu_msssim.py::AMPS[0]
+
+
+def msssim_pair(dt, c, seed=3):
+    """(a, b) as stored: b a tanh-noise image, a = clip(b + 0.1 U(-1, 1)) - the generator's output near its target."""
+    rng = np.random.default_rng(seed)
+    b = np.tanh(1.5 * rng.standard_normal((B, MH, MW, c)))
+    return stored(np.clip(b + M_AMP * rng.uniform(-1, 1, b.shape), -1, 1), dt), stored(b, dt)
+
+
+def msssim_model(a, b, dt, f, old=None, loss0=None, ls_in_grad=True, ls_in_loss=False, scales=None):
+    """The reference's own result as the kernel leaves it: da = round_storage([float(old) +] grad_scale * ls * g), loss word =
+    fp32([loss0 +] loss_scale * loss).  old / loss0: what da / the loss word held (None: stored, not accumulated)."""
+    M = f['scales']
+    loss, _, _ = msssim_ref.loss_and_grad(a.double().numpy(), b.double().numpy(), M, f['power'])
+    m = scales or M
+    _, g, _ = msssim_ref.loss_and_grad(a.double().numpy(), b.double().numpy(), m, f['power'][:m])
+    s = f['ls'] if f['ls'] is not None else 1.0
+    g = g.numpy() * f['grad_scale'] * (s if ls_in_grad else 1.0)
+    da = stored(g + (old.double().numpy() if old is not None else 0.0), dt)
+    term = np.float32(f['loss_scale'] * loss * (s if ls_in_loss else 1.0))
+    return da, float(np.float32(loss0) + term if loss0 is not None else term)
+
+
+@pytest.mark.parametrize('ls', [None, LS], ids=['unscaled', 'loss-scale'])
+@pytest.mark.parametrize('c', [1, 3])
+@pytest.mark.parametrize('dt', DTS)
+def test_msssim_compare(dt, c, ls):
+    a, b = msssim_pair(dt, c)
+    power = tuple(float(np.float32(p)) for p in msssim_ref.POWER[:MS])
+    f = dict(fields(dt, ls), scales=MS, power=power)
+    fa = dict(f, loss_scale=0.84, loss_accumulate=1, grad_scale=84.0, grad_accumulate=1)         # the call of 'msssim_l1'
+    # what gan_l1 left in front of the accumulating call: (1 - alpha) * lambda * ls * sign / count, and its loss word
+    k1 = 16.0 * (ls or 1.0) / a.numel()
+    old = stored(k1 * np.sign(b.double().numpy() - a.double().numpy()), dt)
+    loss0 = float(np.float32(0.16 * np.abs(b.double().numpy() - a.double().numpy()).mean()))
+    assert bool(old.double().abs().max() > 0) and loss0 > 0
+    z = embed(torch.zeros_like(a), 0)
+    da, loss = msssim_model(a, b, dt, f)
+    res = A.msssim_ratios(a, b, z, embed(da, 0), 0, 0.0, loss, f)
+    print(f"msssim {dt} c{c} ls {ls} storing: {res} (smallest factor {A.MSSSIM_PREMISE / res['premise']:.3f})")
+    assert not failed(res), res
+    da_a, loss_a = msssim_model(a, b, dt, fa, old, loss0)
+    res = A.msssim_ratios(a, b, embed(old, 0), embed(da_a, 0), 0, loss0, loss_a, fa)
+    print(f"msssim {dt} c{c} ls {ls} accumulating: {res}")
+    assert not failed(res), res
+    store = lambda da_, loss_, f_=f: failed(A.msssim_ratios(a, b, z, embed(da_, 0), 0, 0.0, loss_, f_))
+    accum = lambda da_, loss_: failed(A.msssim_ratios(a, b, embed(old, 0), embed(da_, 0), 0, loss0, loss_, fa))
+    # the loss and gradient taken against the augmented target
+    assert {'da', 'loss'} <= set(store(*msssim_model(a, augmented(b, dt, c), dt, f)))
+    assert {'da', 'loss'} <= set(accum(*msssim_model(a, augmented(b, dt, c), dt, fa, old, loss0)))
+    # stored where it should accumulate, accumulated where it should store: the gradient, then the loss word
+    assert accum(msssim_model(a, b, dt, fa)[0], loss_a) == ['da']
+    assert failed(A.msssim_ratios(a, b, embed(old, 0), embed(msssim_model(a, b, dt, f, old)[0], 0), 0, loss0, loss, f)) == ['da']
+    assert accum(da_a, msssim_model(a, b, dt, fa)[1]) == ['loss']
+    assert failed(A.msssim_ratios(a, b, z, embed(da, 0), 0, 2.0, msssim_model(a, b, dt, f, loss0=2.0)[1], f)) == ['loss']
+    if ls is not None:            # the scale word on the loss instead of the gradient
+        assert {'da', 'loss'} <= set(store(*msssim_model(a, b, dt, f, ls_in_grad=False, ls_in_loss=True)))
+        assert {'da', 'loss'} <= set(accum(*msssim_model(a, b, dt, fa, old, loss0, ls_in_grad=False, ls_in_loss=True)))
+    # one level fewer: one level's pooling transpose dropped
+    assert store(msssim_model(a, b, dt, f, scales=MS - 1)[0], loss) == ['da']
+    assert accum(msssim_model(a, b, dt, fa, old, loss0, scales=MS - 1)[0], loss_a) == ['da']
+    pad = embed(da, 0)
+    pad[1, 3, 4, c] = 1.0
+    assert store(pad, loss) == ['da untouched outside the view']
+    pad = embed(da_a, 0)
+    pad[0, MH - 1, MW - 1, 7] = -1.0
+    assert failed(A.msssim_ratios(a, b, embed(old, 0), pad, 0, loss0, loss_a, fa)) == ['da untouched outside the view']
+    if dt != 'f32':               # (module docstring: as the dSSIM gradient, at fp32 the max-norm gate is wider than two ulps by construction)
+        top = np.unravel_index(int(da.double().abs().argmax()), tuple(da.shape))
+        assert store(bump(da, top, 2), loss) == ['da']
+    # independent operands: the gate's premise does not hold, and the row says so
+    ind = stored(A.lattice((B, MH, MW, c), 4).numpy(), dt)
+    da_i, loss_i = msssim_model(b, ind, dt, f)                # (the tanh image against a lattice one, with the reference's own result)
+    res = A.msssim_ratios(b, ind, z, embed(da_i, 0), 0, 0.0, loss_i, f)
+    print(f"msssim {dt} c{c} independent operands: smallest factor {A.MSSSIM_PREMISE / res['premise']:.4f}")
+    assert 'premise' in failed(res), res
 
 
 # ---- DiffAugment ----------------------------------------------------------------------------------------------------------------------
@@ -313,6 +398,29 @@ def test_the_striking_and_mapping_rule():
     pools = [('gan_copy_view', None), ('gan_pool_exchange', A.ANY), ('gan_conv2d_fwd', A.ANY), ('gan_lsq_logits', A.ANY), ('gan_lsq_logits', A.ANY)]
     assert not A.same_as_plain(pools, pools_plain)
     assert A.same_as_plain(pools[:-1], pools_plain)
+
+
+def test_the_rule_places_gan_msssim_by_the_generator_loss():
+    K1 = ('conv', 0, 64, 64)
+    plain = [('gan_pack_multi', None), ('gan_conv2d_fwd', K1), ('gan_l1', None), ('gan_copy_view', None), ('gan_conv2d_fwd', K1),
+             ('gan_patchgan_losses', None)]
+    ms, l1, edge = ('gan_msssim', A.ANY), ('gan_l1', None), ('gan_edge_l1', A.ANY)
+    seq = lambda *sec: plain[:2] + list(sec) + plain[3:]
+    # 'msssim': gan_msssim stands where gan_l1 stood; 'msssim_l1': gan_l1 stays, gan_msssim is the extra call behind it
+    assert not A.same_as_plain(seq(ms), plain, msssim='msssim') and not A.same_as_plain(seq(ms, edge), plain, msssim='msssim')
+    assert not A.same_as_plain(seq(l1, ms), plain, msssim='msssim_l1') and not A.same_as_plain(seq(l1, ms, edge), plain, msssim='msssim_l1')
+    # the place is the caller's to name: the other place, or none, does not fit
+    assert A.same_as_plain(seq(ms), plain, msssim='msssim_l1') and A.same_as_plain(seq(l1, ms), plain, msssim='msssim')
+    assert A.same_as_plain(seq(ms), plain) and A.same_as_plain(seq(l1, ms), plain)
+    assert A.same_as_plain(seq(l1), plain, msssim='msssim') and A.same_as_plain(seq(l1), plain, msssim='msssim_l1')      # no gan_msssim at all
+    assert A.same_as_plain(seq(ms, edge), plain, msssim='msssim_l1')                                 # 'msssim_l1' without its gan_l1
+    assert A.same_as_plain(seq(ms, ms), plain, msssim='msssim')                                      # a second gan_msssim
+    assert A.same_as_plain(seq(l1, ms, ms), plain, msssim='msssim_l1') and A.same_as_plain(seq(l1, ms, edge, ms), plain, msssim='msssim_l1')
+    assert A.same_as_plain(seq(edge, ms), plain, msssim='msssim')                                    # recorded after the edge term
+    assert A.same_as_plain(seq(l1, edge, ms), plain, msssim='msssim_l1')
+    assert A.same_as_plain(seq(ms, l1), plain, msssim='msssim_l1')                                   # in front of its gan_l1
+    with pytest.raises(AssertionError):
+        A.same_as_plain(seq(ms), plain, msssim='dssim')
 
 
 def test_every_option_entry_point_has_a_checker_and_a_plan():

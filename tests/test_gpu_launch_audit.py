@@ -9,7 +9,7 @@ both sizes, CycleGAN at 256x256).  fp32 beyond the one case here, CycleGAN at 51
 of the plan classes that no case here reaches, per dtype family.  At channels = 3 the
 image-side layers leave the one-kernel thin-N form for conv_thin_n_kernel + conv_thin_col2im_kernel, which no case here launches:
 tests/test_gpu_rgb_audit.py audits the launches that depend on the channel count.  Every step here is built without options:
-the launches of gan_dssim, gan_edge_l1, gan_diffaug_draw / gan_diffaug_apply, gan_lsq_logits / gan_patchgan_losses_lsq,
+the launches of gan_dssim, gan_msssim, gan_edge_l1, gan_diffaug_draw / gan_diffaug_apply, gan_lsq_logits / gan_patchgan_losses_lsq,
 gan_pool_exchange and gan_adam_begin_sched inside the option-carrying captured steps are tests/test_gpu_option_audit.py's (their
 device-free compare functions: tests/test_cpu_option_audit.py)."""
 import time

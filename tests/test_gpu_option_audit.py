@@ -1,17 +1,21 @@
-"""The option-carrying training steps per launch against fp64 (tests/launch_audit.py): dSSIM, the Sobel edge term,
-DiffAugment, the least-squares GAN loss, the learning-rate schedule and CycleGAN's image pools, in the captured, laned step, at f32 /
-bf16 / f16 and at channels 1 and 3.  Every case is at 256x256; batch 2 for Pix2Pix (the smallest at which no BatchNorm layer sees one
-value per channel), 1 for CycleGAN.
+"""The option-carrying training steps per launch against fp64 (tests/launch_audit.py): dSSIM, MS-SSIM alone and mixed
+with L1, the Sobel edge term, DiffAugment, the least-squares GAN loss, the learning-rate schedule and CycleGAN's image pools, in the
+captured, laned step, at f32 / bf16 / f16 and at channels 1 and 3.  Every case is at 256x256 (for MS-SSIM's five scales the smallest
+size the U-Net admits: 176 is the minimum side); batch 2 for Pix2Pix (the smallest at which no BatchNorm layer sees one value per
+channel), 1 for CycleGAN.  An MS-SSIM case runs on a target near the generator's own output (launch_audit.near_target, amplitude
+NEAR_AMP): the loss gate of gan_msssim is derived for factors of at least 0.4, which an untrained generator against an independent
+lattice image does not give; the checker's 'premise' row holds the inputs to it, from the reference alone.
 
 Per case:
-  a. the audit: replay(check=option_call(...)) checks the calls of the eight option entry points and every conv / dgrad / wgrad call
+  a. the audit: replay(check=option_call(...)) checks the calls of the nine option entry points and every conv / dgrad / wgrad call
      with an operand in a buffer only the option creates (aug_raw, aug_dgen, the pooled third of D's batch); the rest is issued
      unchecked and carries AS_ONE_GPU, which it earns against the same step built without the options in the same test
      (launch_audit.same_as_plain); every option entry point the case was built for is among the checked rows the expected number of times;
   b. the wiring, from the recorded descriptors' pointers and scalars;
   c. the captured graph against the serial order: one graph launch and one unchecked one-stream re-issue of the recorded calls from
      the same start leave the same bits in the losses, every network's grad / master / m / v / step, every image-side buffer, the
-     DiffAugment table and counter and the pools - the one-stream audit cannot see a missing dependency edge between lanes;
+     DiffAugment table and counter, the pools and the MS-SSIM workspace (2 M + 1 launches on the side lane beside D's forward, gan_l1
+     in front and gan_edge_l1 behind on the same g.dgen) - the one-stream audit cannot see a missing dependency edge between lanes;
   d. the pad channels of every image-side buffer (aug_raw and aug_dgen among them) are bit-zero before the first and after the last call;
   e. f16: the loss-scale state after the replay is that of a finite, applied step."""
 import gc
@@ -30,6 +34,8 @@ pytestmark = pytest.mark.gpu
 ALL = 'translation,cutout,brightness,saturation'
 W_EDGE = 0.25
 SCHED = (STEP_SCHEDULE[0], STEP_SCHEDULE[1], STEP_SCHEDULE[2])        # (decay_start, decay_end, end_factor)
+MSSSIM = ('msssim', 'msssim_l1')
+NEAR_AMP = 0.1               # tests/test_gpu_msssim.py::AMPS[0].  Were the reference's smallest factor under 0.4 on a case: 0.05, then 0.025
 CASES = [
     ('pix2pix', 'bf16', 1, dict(generator_loss='dssim', edge_weight=W_EDGE, diffaug=ALL, gan_loss='lsgan', lr_schedule=SCHED)),
     ('pix2pix', 'f16', 1, dict(generator_loss='dssim', edge_weight=W_EDGE)),
@@ -38,12 +44,17 @@ CASES = [
     ('pix2pix', 'f32', 3, dict(edge_weight=W_EDGE, diffaug=ALL)),
     ('cyclegan', 'bf16', 1, dict(pools=A.POOL_CAPACITY, gan_loss='lsgan', lr_schedule=SCHED)),
     ('cyclegan', 'f16', 3, dict(pools=A.POOL_CAPACITY)),
+    ('pix2pix', 'bf16', 1, dict(generator_loss='msssim', edge_weight=W_EDGE, diffaug=ALL, gan_loss='lsgan', lr_schedule=SCHED)),
+    ('pix2pix', 'f16', 1, dict(generator_loss='msssim')),                     # the storing form under a loss-scale word
+    ('pix2pix', 'f16', 3, dict(generator_loss='msssim_l1', edge_weight=W_EDGE)),           # the product's default alpha, 0.84
+    ('pix2pix', 'f32', 3, dict(generator_loss='msssim_l1', msssim_alpha=0.5, diffaug=ALL)),
 ]
 
 
 def case_id(case):
     model, dtype, ch, opts = case
-    tags = [('dssim', opts.get('generator_loss') == 'dssim'), ('edge', opts.get('edge_weight')), ('diffaug', opts.get('diffaug')),
+    tags = [('dssim', opts.get('generator_loss') == 'dssim'), ('msssim', opts.get('generator_loss') == 'msssim'),
+            ('msssim_l1', opts.get('generator_loss') == 'msssim_l1'), ('alpha', opts.get('msssim_alpha')), ('edge', opts.get('edge_weight')), ('diffaug', opts.get('diffaug')),
             ('lsgan', opts.get('gan_loss') == 'lsgan'), ('sched', opts.get('lr_schedule')), ('pools', opts.get('pools'))]
     return f"{model}-{dtype}-ch{ch}-" + '+'.join(t for t, on in tags if on)
 
@@ -54,6 +65,8 @@ def expected_counts(model, opts):
     n = {}
     if opts.get('generator_loss') == 'dssim':
         n['gan_dssim'] = 1
+    if opts.get('generator_loss') in MSSSIM:
+        n['gan_msssim'] = 1
     if opts.get('edge_weight'):
         n['gan_edge_l1'] = 1
     if opts.get('diffaug'):
@@ -80,6 +93,8 @@ def kept(st):
         out['diffaug.launches'], out['diffaug.table'] = st.diffaug.tensors()
     for i, pool in enumerate(getattr(st, 'pools', None) or ()):
         out[f'pool{i}.state'], out[f'pool{i}.storage'] = pool.tensors()
+    if hasattr(st, 'msssim_ws'):
+        out['msssim_ws'] = st.msssim_ws
     if st.ctx.ls is not None:
         out['loss scale'] = st.ctx.ls
     torch.cuda.synchronize()
@@ -97,7 +112,44 @@ def pix2pix_wiring(st, calls, dtype, opts):
     if (ls_ptr != 0) != (dtype == 'f16'):
         bad.append(f"loss-scale state {ls_ptr:#x} at {dtype}")
     want = dict(a=key(g.out_view()), b=key(raw.view(C, C, 0, B)), da=key(g.dgen.view(0, C)), loss_out=st.losses.data_ptr() + 8, scale_state=ls_ptr)
-    if opts.get('generator_loss') == 'dssim':
+    kind = opts.get('generator_loss', 'l1')
+    f32 = lambda v: float(np.float32(v))
+    if kind in MSSSIM:
+        # gan_msssim alone, or directly behind gan_l1 and accumulating into its loss word and gradient; the scalars as the fp32
+        # values the step's own double products (steps.py: loss_scale * al, grad_scale * (1.0 - al), ...) round to
+        al = st.msssim_alpha if kind == 'msssim_l1' else 1.0
+        if kind == 'msssim_l1' and al != opts.get('msssim_alpha', 0.84):
+            bad.append(f"msssim_alpha {al}")
+        (i,) = at('gan_msssim')
+        s = calls[i].args[0]._obj
+        got = dict(a=key(s.a), b=key(s.b), da=key(s.da), loss_out=A._void(s.loss_out), scale_state=A._void(s.scale_state))
+        if got != want:
+            bad.append(f"gan_msssim: {got}, expected {want}")
+        acc = int(kind == 'msssim_l1')
+        sc = (s.loss_scale, s.loss_accumulate, s.grad_scale, s.grad_accumulate)
+        if sc != ((1.0, 0, f32(st.lam), 0) if not acc else (f32(1.0 * al), 1, f32(st.lam * al), 1)):
+            bad.append(f"gan_msssim scalars (loss scale, accumulate, grad scale, accumulate) {sc} at alpha {al}")
+        if (A._void(s.workspace), s.workspace_bytes) != (st.msssim_ws.data_ptr(), st.msssim_ws.numel() * 4):
+            bad.append(f"gan_msssim workspace {A._void(s.workspace):#x} + {s.workspace_bytes}")
+        if s.scales != 5 or list(s.power) != list(A.L.msssim_power(5)) or A._void(s.per_image):
+            bad.append(f"gan_msssim scales {s.scales} power {list(s.power)} per_image {A._void(s.per_image):#x}")
+        if (s.dtype_a, s.dtype_b, s.dtype_da) != (st.ctx.dt,) * 3:
+            bad.append(f"gan_msssim dtypes {(s.dtype_a, s.dtype_b, s.dtype_da)}")
+        l1 = at('gan_l1')
+        if not acc:
+            if l1:
+                bad.append(f"'msssim' records gan_l1 at {l1}")
+        elif l1 != [i - 1]:
+            bad.append(f"'msssim_l1': gan_l1 at {l1}, gan_msssim at {i}")
+        else:
+            a_ = calls[i - 1].args
+            got = dict(a=key(a_[1]._obj), b=key(a_[2]._obj), da=key(a_[7]._obj), loss_out=A._void(a_[5]), scale_state=A._void(a_[9]))
+            if got != want:
+                bad.append(f"gan_l1 of 'msssim_l1': {got}, expected {want}")
+            sc = (f32(a_[3]), a_[4], f32(a_[6]))
+            if sc != (f32(1.0 * (1.0 - al)), 0, f32(st.lam * (1.0 - al))):
+                bad.append(f"gan_l1 scalars of 'msssim_l1' (loss scale, accumulate, grad scale) {sc} at alpha {al}")
+    elif kind == 'dssim':
         (i,) = at('gan_dssim')
         s = calls[i].args[0]._obj
         got = dict(a=key(s.a), b=key(s.b), da=key(s.da), loss_out=A._void(s.loss_out), scale_state=A._void(s.scale_state))
@@ -107,20 +159,24 @@ def pix2pix_wiring(st, calls, dtype, opts):
         a_ = calls[i].args
         got = dict(a=key(a_[1]._obj), b=key(a_[2]._obj), da=key(a_[7]._obj), loss_out=A._void(a_[5]), scale_state=A._void(a_[9]))
         sec = (a_[3], a_[4], a_[6])
-    if got != want:
-        bad.append(f"secondary loss: {got}, expected {want}")
-    if sec != (1.0, 0, np.float32(st.lam)):
-        bad.append(f"secondary loss scalars (loss scale, accumulate, grad scale) {sec}")
-    (j,) = at('gan_edge_l1')
-    e = calls[j].args[0]._obj
-    got = dict(a=key(e.a), b=key(e.b), da=key(e.da), loss_out=A._void(e.loss_out), scale_state=A._void(e.scale_state))
-    if got != want:
-        bad.append(f"edge term: {got}, expected {want}")
-    w = st.edge_weight
-    if (e.loss_accumulate, e.grad_accumulate, e.loss_scale, e.grad_scale) != (1, 1, np.float32(w), np.float32(st.lam * w)):
-        bad.append(f"edge term scalars {(e.loss_accumulate, e.grad_accumulate, e.loss_scale, e.grad_scale)}")
-    if not j > i:
-        bad.append(f"edge term recorded at {j}, the secondary loss at {i}")
+    if kind not in MSSSIM:
+        if got != want:
+            bad.append(f"secondary loss: {got}, expected {want}")
+        if sec != (1.0, 0, np.float32(st.lam)):
+            bad.append(f"secondary loss scalars (loss scale, accumulate, grad scale) {sec}")
+    if opts.get('edge_weight'):
+        (j,) = at('gan_edge_l1')
+        e = calls[j].args[0]._obj
+        got = dict(a=key(e.a), b=key(e.b), da=key(e.da), loss_out=A._void(e.loss_out), scale_state=A._void(e.scale_state))
+        if got != want:
+            bad.append(f"edge term: {got}, expected {want}")
+        w = st.edge_weight
+        if (e.loss_accumulate, e.grad_accumulate, e.loss_scale, e.grad_scale) != (1, 1, np.float32(w), np.float32(st.lam * w)):
+            bad.append(f"edge term scalars {(e.loss_accumulate, e.grad_accumulate, e.loss_scale, e.grad_scale)}")
+        if not j > i:                     # (i: the secondary loss - with an MS-SSIM loss the gan_msssim call, behind its gan_l1)
+            bad.append(f"edge term recorded at {j}, the secondary loss at {i}")
+    elif at('gan_edge_l1'):
+        bad.append(f"a step without an edge weight records gan_edge_l1 at {at('gan_edge_l1')}")
     if aug is None:
         return bad
     (k,) = at('gan_diffaug_draw')
@@ -189,8 +245,11 @@ def test_option_step_per_launch_against_fp64(case, monkeypatch):
     gc.collect()
     st, calls, replay_, start = A.option_step(model, dtype, ch, batch, monkeypatch, **opts)
     ctx = st.ctx
+    msssim = opts.get('generator_loss') if opts.get('generator_loss') in MSSSIM else None
+    if msssim:                  # before anything is compared: the target near G's own output, part of the known start from here on
+        A.near_target(st, start, NEAR_AMP)
     check = A.option_call(A.option_regions(st))
-    bad = A.same_as_plain(A.sequence_of(calls, check), plain, replaced)
+    bad = A.same_as_plain(A.sequence_of(calls, check), plain, replaced, msssim=msssim)
     assert not bad, "the unchecked calls are not those of the plain step:\n" + '\n'.join(bad)
     # b. wiring
     bad = (pix2pix_wiring if model == 'pix2pix' else cyclegan_wiring)(st, calls, dtype, opts)
@@ -241,6 +300,11 @@ def test_option_step_per_launch_against_fp64(case, monkeypatch):
         assert sorted(traces) == ['keep', 'swap'], traces
     if not opts.get('diffaug') and not opts.get('pools'):
         assert not convs
+    if msssim:
+        (ms,) = [r[4] for r in rows if r[1] == 'gan_msssim']
+        print(f"[{title}] gan_msssim at amplitude {NEAR_AMP}: smallest factor of the reference {A.MSSSIM_PREMISE / ms['premise']:.3f}; error / gate " +
+              ', '.join(f"{k} {v:.3f}" for k, v in ms.items()))
+        assert set(ms) == {'premise', 'da', 'loss', 'da untouched outside the view'}
     assert not before and not after, f"pad channels: before the first call {before}, after the last {after}"
     bad = A.failures(rows)
     assert not bad, "calls outside their gates:\n" + '\n'.join(f"  {b}" for b in bad[:40])
