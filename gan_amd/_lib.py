@@ -111,6 +111,20 @@ class GanAugmentDesc(_Desc):
                 ("lut", C.c_void_p), ("dst_a", C.c_void_p), ("dst_b", C.c_void_p), ("samples", C.c_void_p)]
 
 
+PREPROCESS_MAX_REGIONS = 64
+PRE_CLAHE, PRE_BLUR, PRE_SHARPEN = 1, 2, 4
+
+
+class GanPreRegion(C.Structure):
+    _fields_ = [("src_offset", C.c_int64), ("pitch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32)]
+
+
+class GanPreprocessDesc(_Desc):
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("c", C.c_int32), ("stages", C.c_uint32), ("src", C.c_void_p),
+                ("src_bytes", C.c_int64), ("clip", C.c_float), ("grid", C.c_int32), ("sigma", C.c_float), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("regions", C.c_void_p)]
+
+
 class GanQualityDesc(_Desc):
     _fields_ = [("struct_size", C.c_uint32), ("dtype_a", C.c_int32), ("dtype_b", C.c_int32), ("a", GanTensor), ("b", GanTensor),
                 ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
@@ -260,6 +274,8 @@ SYMBOLS = {
     "gan_grad_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gan_grad_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "gan_augment_u8": (C.c_int, [C.POINTER(GanAugmentDesc), C.c_void_p]),
+    "gan_preprocess_workspace_bytes": (C.c_size_t, [C.POINTER(GanPreprocessDesc)]),
+    "gan_preprocess_u8": (C.c_int, [C.POINTER(GanPreprocessDesc), C.c_void_p]),
     "gan_image_quality_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "gan_image_quality": (C.c_int, [C.POINTER(GanQualityDesc), C.c_void_p]),
     "gan_dssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

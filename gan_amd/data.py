@@ -202,12 +202,15 @@ class DeviceDataset:
       kind 'pair'   (Pix2Pix): split at w // 2, each half resized by nearest_index(side, L)
       kind 'single' (CycleGAN): resized to size, then to L: the composition nearest_index(side, size)[nearest_index(size, L)]
     with L = size + 30 for the jittered (training) form and L = size for the validation / test form.  One table per distinct
-    source side length.  `cap_bytes`: the decoded bytes are added up from the image headers before anything is decoded or
+    source side length.  `preprocess_a` / `preprocess_b` (gan_amd/preprocess.py): run once over the resident
+    buffer behind the upload, before any batch is built - over the input half (a) and the target half (b) of every pair, or over
+    the whole image of kind 'single' (preprocess_a only).  `cap_bytes`: the decoded bytes are added up from the image headers before anything is decoded or
     allocated; more than the cap is an error (no fall-back to the host pipeline)."""
 
     DECODE_WORKERS = 16
 
-    def __init__(self, files, channels, size, device, kind='pair', jitter=True, orient='left', cap_bytes=64 << 30):
+    def __init__(self, files, channels, size, device, kind='pair', jitter=True, orient='left', cap_bytes=64 << 30,
+                 preprocess_a=None, preprocess_b=None):
         from PIL import Image
         assert kind in ('pair', 'single') and orient in ('left', 'right') and int(channels) in (1, 3)
         self.files, self.c, self.size, self.device = list(files), int(channels), int(size), device
@@ -261,6 +264,17 @@ class DeviceDataset:
         self.src = torch.from_numpy(host).to(device)                # one upload
         self.tables = torch.from_numpy(np.stack(tables) if tables else np.zeros((1, self.table_len), np.int32)).to(device)
         self.lut = torch.from_numpy(normalize_table()).to(device)
+        assert kind == 'pair' or not preprocess_b, "a 'single' dataset has one region per image: preprocess_a"
+        # (offset, pitch, first column a, first column b) are the meta's; the sides come from the header sizes
+        for pre, col in ((preprocess_a, 2), (preprocess_b, 3)):
+            if not pre or (col == 3 and kind != 'pair'):
+                continue
+            regions = []
+            for (h, w), m in zip(dims, self.meta):
+                half = w // 2
+                width = w if kind == 'single' else (half if m[col] == 0 else w - half)
+                regions.append((m[0] + m[col] * self.c, m[1], h, width))
+            pre.apply_device(self.src, regions, channels=self.c)      # enqueue-only, chunks of 64 regions inside the call
 
 
     def augment(self, idx, draws, out=None):

@@ -15,6 +15,7 @@ from . import ddp
 from . import tiling
 from .base_gan import GAN
 from .diffaug import DiffAugment, parse_policies
+from .preprocess import MAX_GRID, MAX_SIGMA, Preprocess, parse_stages
 from .quality import QualityMeter, image_quality, summary
 from .steps import Pix2PixStep
 from .runner import (RESUME_SLOTS, add_common_flags, add_prediction_flags, check_common_flags, check_prediction_flags, drive, finite_lists,
@@ -93,14 +94,42 @@ class Pix2Pix(GAN):
         self.generator_optimizer = mk().bind(self.generator.net.params)
         self.discriminator_optimizer = mk().bind(self.discriminator.net.params)
         (self.generator_ema,) = self._init_trainer(averaged=(self.generator,))
+        self._preprocessors = None
         self.diffaug = None        # --diffaugment: one DiffAugment for the training steps of every batch size (built with the first of them)
 
     def networks(self):
         return (self.generator, self.discriminator)
 
     # ---- input pipeline (pix2pix.py:34-165) ------------------------------------------------------
+    def preprocessors(self):
+        """(input half, target half): the Preprocess of --preprocess-input / --preprocess-target; both empty
+        without the flags."""
+        if self._preprocessors is None:
+            cfg = self.config
+            kw = dict(clip=float(cfg.get('clahe_clip', 1.0)), grid=int(cfg.get('clahe_grid', 15)), sigma=float(cfg.get('blur_sigma', 0.5)))
+            self._preprocessors = tuple(Preprocess(cfg.get(k) or '', **kw) for k in ('preprocess_input', 'preprocess_target'))
+        return self._preprocessors
+
+    def preprocess_pair(self, img):
+        """The decoded uint8 pair with each half run through its Preprocess, a half being a region of its own (the very bytes
+        DeviceDataset(preprocess_a=, preprocess_b=) leaves in the resident buffer); the image itself without the flags."""
+        pa, pb = self.preprocessors()
+        if not pa and not pb:
+            return img
+        H, W = img.shape[:2]
+        first, second = (0, 0, H, W // 2), (0, W // 2, H, W - W // 2)
+        ra, rb = (first, second) if self.config['input_img_orient'] == 'left' else (second, first)
+        for pre, region in ((pa, ra), (pb, rb)):
+            if pre:
+                img = pre.apply_host(img, [region])
+        return img
+
     def split_img(self, image_file: str):
-        return D.split_img(super().load(image_file, resize=False), self.config['input_img_orient'])
+        pa, pb = self.preprocessors()
+        if not pa and not pb:
+            return D.split_img(super().load(image_file, resize=False), self.config['input_img_orient'])
+        img = self.preprocess_pair(D.decode(image_file, int(self.config['channels'])))       # uint8, before the cast of `load`
+        return D.split_img(img.astype(np.float32), self.config['input_img_orient'])
 
     def random_crop(self, input_image, real_image, height: int, width: int):
         y, x = self._rng.integers(0, input_image.shape[0] - height + 1), self._rng.integers(0, input_image.shape[1] - width + 1)
@@ -132,8 +161,9 @@ class Pix2Pix(GAN):
         bs = self.config["batch_size"]
         if self.config.get('data_cache', 'host') == 'device':        # decoded once, augmented by gan_augment_u8
             cap = int(float(self.config.get('data_cache_gb', 64)) * 2**30)
+            pa, pb = self.preprocessors()
             ds = lambda files, jitter: D.DeviceDataset(full(files), int(self.config['channels']), self.config['img_size'], dev, 'pair',
-                                                       jitter, self.config['input_img_orient'], cap)
+                                                       jitter, self.config['input_img_orient'], cap, preprocess_a=pa, preprocess_b=pb)
             return (D.DeviceBatches(ds(train, True), bs, lambda: D.draw_jitter(self._rng), make_example=self.process_images_train),
                     D.DeviceBatches(ds(val, False), bs, make_example=self.process_images_pred),
                     D.DeviceBatches(ds(test, False), bs, make_example=self.process_images_pred))
@@ -301,6 +331,7 @@ class Pix2Pix(GAN):
                 raise ValueError(f"{f}: each half is {H} x {half}, smaller than --img-size {S}; --predict-resolution native does "
                                  "not pad (use --predict-resolution resized)")
             ci, ct = (0, half) if self.config['input_img_orient'] == 'left' else (half, 0)
+            img = self.preprocess_pair(img)          # (the widths are even here: the halves are the regions of the training data)
             src = torch.from_numpy(img.copy()).to(self.ctx.device)      # the one upload
             pred = self.generator.infer_tiled(src, tile=S, overlap=V, col0=ci, width=half, fold=False)
             if meter is not None:
@@ -311,10 +342,11 @@ class Pix2Pix(GAN):
 
 
 class Options(argparse.Namespace):
-    """The parsed Pix2Pix command line.  --diffaugment, --edge-weight and --msssim-alpha are this driver's own training options: they live in slots beside the flag
+    """The parsed Pix2Pix command line.  --diffaugment, --edge-weight, --msssim-alpha and the preprocessing flags are this driver's own training options: they live in slots beside the flag
     dictionary (vars(opt) stays the set of flags the two drivers are compared on) and reaches the model's config - and
     config.json - through runner.config_of."""
-    __slots__ = ('diffaugment', 'edge_weight', 'msssim_alpha') + RESUME_SLOTS
+    __slots__ = ('diffaugment', 'edge_weight', 'msssim_alpha', 'preprocess_input', 'preprocess_target', 'clahe_clip', 'clahe_grid',
+                 'blur_sigma') + RESUME_SLOTS
 
 
 def parse_opt(argv=None):
@@ -339,6 +371,16 @@ def parse_opt(argv=None):
                         help="weight W of a Sobel edge term added to the secondary generator loss, relative to --lambda: the generator "
                              "minimises gan + lambda * (secondary + W * mean |Sobel(generated - target)|); default 0: no edge term "
                              "(the reference)")
+    stages_help = ("a comma-separated subset of clahe,blur,sharpen, applied in that order to the decoded uint8 {half} half of every pair "
+                   "at read-in, on the GPU with --data-cache device: contrast-limited adaptive histogram equalisation (--clahe-clip, "
+                   "--clahe-grid), a Gaussian blur (--blur-sigma), a 3 x 3 sharpening filter; the half is a region of its own "
+                   "(reflected borders) and every channel of an RGB image is processed as its own plane (per-channel equalisation, "
+                   "no colour-space conversion); training, validation, test and --predict all see the same bytes; default: none")
+    parser.add_argument('--preprocess-input', type=str, default='', metavar='STAGES', help=stages_help.format(half='input'))
+    parser.add_argument('--preprocess-target', type=str, default='', metavar='STAGES', help=stages_help.format(half='target'))
+    parser.add_argument('--clahe-clip', type=float, default=1.0, help="CLAHE clip limit as cv2.createCLAHE's clipLimit, >= 0 (0: no clipping); default 1.0")
+    parser.add_argument('--clahe-grid', type=int, default=15, help=f"CLAHE tiles per side (tileGridSize), 1 .. {MAX_GRID}; default 15")
+    parser.add_argument('--blur-sigma', type=float, default=0.5, help=f"sigma of the blur stage, 0 < sigma <= {MAX_SIGMA}; default 0.5")
     parser.add_argument('--input-img-orient', type=str, default='left', choices=['left', 'right'], help='whether input image is on left (i.e. target right) or vice-versa')
     parser.add_argument('--lambda', type=int, default=100, help='lambda value for secondary generator loss (L1 / dSSIM)')
     add_prediction_flags(parser, image='half', resized=' (the reference)',
@@ -361,6 +403,15 @@ def parse_opt(argv=None):
         parser.error(f"--msssim-alpha {args.msssim_alpha} must be a weight in (0, 1]")
     if not args.edge_weight >= 0.0 or args.edge_weight == float('inf'):
         parser.error(f"--edge-weight {args.edge_weight} must be a finite weight >= 0")
+    for flag in ('preprocess_input', 'preprocess_target'):
+        try:
+            setattr(args, flag, ','.join(parse_stages(getattr(args, flag))))       # (canonical order: what config.json records)
+        except ValueError as e:
+            parser.error(f"--{flag.replace('_', '-')}: {e}")
+    try:
+        Preprocess((), args.clahe_clip, args.clahe_grid, args.blur_sigma)
+    except ValueError as e:
+        parser.error(f"--clahe-clip / --clahe-grid / --blur-sigma: {e}")
     try:
         args.diffaugment = ','.join(parse_policies(args.diffaugment))        # (canonical order: what config.json records)
     except ValueError as e:

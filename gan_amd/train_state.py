@@ -29,8 +29,9 @@ CONFIG_KEYS = ('batch_size', 'img_size', 'channels', 'dtype', 'seed', 'learning_
                'validation_size', 'test_img', 'input_img_orient')
 PATH_KEYS = ('data', 'input_images', 'target_images')
 # run-defining keys that joined after checkpoints were first written: a stored config without one holds its default
-LATER_KEYS = ('edge_weight', 'msssim_alpha')
-_DEFAULTS = {'edge_weight': 0.0, 'msssim_alpha': 0.84, 'diffaugment': '', 'pool_size': 0, 'ema_decay': 0.0, 'lr_decay_epochs': 0, 'lr_end_factor': 0.0, 'gan_loss': 'bce',
+LATER_KEYS = ('edge_weight', 'msssim_alpha', 'preprocess_input', 'preprocess_target', 'clahe_clip', 'clahe_grid', 'blur_sigma')
+_DEFAULTS = {'edge_weight': 0.0, 'msssim_alpha': 0.84, 'preprocess_input': '', 'preprocess_target': '', 'clahe_clip': 1.0, 'clahe_grid': 15,
+             'blur_sigma': 0.5, 'diffaugment': '', 'pool_size': 0, 'ema_decay': 0.0, 'lr_decay_epochs': 0, 'lr_end_factor': 0.0, 'gan_loss': 'bce',
              'data_cache': 'host', 'ema_warmup': 'true', 'dtype': 'bf16', 'seed': 123}
 
 

@@ -612,6 +612,56 @@ typedef struct GanAugmentDesc {
  * them are found before anything is launched. */
 int gan_augment_u8(const GanAugmentDesc* d, gan_stream_t stream);
 
+/* Image preprocessing of the resident uint8 images, once, before any batch is built: the chain of the reference's curation script
+ * (create_training_imgs/curate_FLIR_data.py: cv2.createCLAHE(clipLimit=1.0, tileGridSize=(15, 15)), a Gaussian blur of sigma
+ * 0.5, a 3 x 3 sharpening filter), in place.  A REGION is a height x width window of a c-channel interleaved image with its own
+ * row pitch (each half of a Pix2Pix pair is one); every channel is its own plane (per-channel equalisation, no colour-space
+ * conversion).  A stage reads no byte outside its region: borders are reflect-101 of the region itself.  The stages run in the
+ * fixed order CLAHE, blur, sharpen, each on the previous stage's bytes; the arithmetic is DESIGN.md section 25:
+ *   CLAHE   OpenCV's 8-bit algorithm with tilesX = tilesY = grid: reflect-pad right / bottom to a multiple of grid, per tile a
+ *           256-bin histogram, clipped at max(int(clip * area / 256), 1) (clip = 0: no clipping) and redistributed, a table
+ *           rint(cumsum * float(255 / area)), then per pixel the bilinear blend of four tables in fp32 without contraction.
+ *   blur    integer taps q[-r .. r] summing to 256 (r = (int(rint(6 sigma + 1)) | 1) / 2; q_i = rint(256 w_i), the centre takes the
+ *           remainder), a horizontal and a vertical pass, out = (sum + 32768) >> 16.
+ *   sharpen clamp(5 p - up - down - left - right, 0, 255).
+ * clip and sigma are taken as the doubles their float values convert to.  Bytes of src outside the regions are not written.
+ * Regions of one call must not overlap.  n may be any positive number: the regions travel to the kernels by value,
+ * GAN_PREPROCESS_MAX_REGIONS per launch, and the launches of one group of regions reuse the workspace behind those of the group
+ * before (stream order). */
+typedef struct GanPreRegion {
+  int64_t src_offset;  /* byte offset of the region's first byte (row 0, column 0, channel 0) in src */
+  int32_t pitch;       /* bytes between consecutive rows, >= width * c */
+  int32_t height;      /* rows */
+  int32_t width;       /* pixels per row */
+} GanPreRegion;
+
+enum { GAN_PREPROCESS_MAX_REGIONS = 64 };
+enum { GAN_PRE_CLAHE = 1, GAN_PRE_BLUR = 2, GAN_PRE_SHARPEN = 4 };
+
+typedef struct GanPreprocessDesc {
+  uint32_t struct_size;
+  int32_t n;                   /* regions, >= 1 */
+  int32_t c;                   /* channels, interleaved: 1 or 3 */
+  uint32_t stages;             /* GAN_PRE_* bits, at least one */
+  uint8_t* src;                /* device: the packed uint8 images */
+  int64_t src_bytes;           /* size of that buffer */
+  float clip;                  /* CLAHE clip limit, finite and >= 0 (0: no clipping) */
+  int32_t grid;                /* CLAHE tiles per side, 1 ..= 32 */
+  float sigma;                 /* blur: 0 < sigma <= 1.5 */
+  void* workspace;             /* device: >= gan_preprocess_workspace_bytes(d), 16-byte aligned */
+  size_t workspace_bytes;
+  const GanPreRegion* regions; /* HOST array of n entries, read at call time */
+} GanPreprocessDesc;
+
+/* Bytes of workspace the call needs (the tile tables and one dense copy of each region, of the largest group of
+ * GAN_PREPROCESS_MAX_REGIONS regions); 0 for a descriptor gan_preprocess_u8 refuses (src, workspace and src_bytes are not looked at). */
+size_t gan_preprocess_workspace_bytes(const GanPreprocessDesc* d);
+/* GAN_E_ARG: NULL pointer, wrong struct_size, n < 1, c not 1 or 3, stages 0 or with unknown bits, a region outside src or with
+ * pitch < width * c, grid outside 1 .. 32, sigma outside (0, 1.5], clip negative or not finite, workspace not 16-byte aligned.
+ * GAN_E_SHAPE: a side shorter than grid (CLAHE), than r + 1 (blur) or than 2 (sharpen), or (height - 1) * pitch + width * c >= 2^31.
+ * GAN_E_WORKSPACE: workspace too small.  All found before anything is launched; enqueue-only. */
+int gan_preprocess_u8(const GanPreprocessDesc* d, gan_stream_t stream);
+
 /* ---- image-quality metrics ---------------------------------------------------------------------- */
 /* Per image of a batch of pairs, on the display range u = 0.5 * x + 0.5 (the mapping generate_images plots, pix2pix.py:236; inputs in
  * [-1, 1], max_val = 1): out[i] = {ssim, psnr, mae, mse}.
